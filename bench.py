@@ -97,7 +97,11 @@ def parse(argv=None):
     ap.add_argument("--no-reference-protocol", action="store_true")
     ap.add_argument("--no-rollout", action="store_true", help="time (ii)-(iv) only (the reference's Train___Time)")
     ap.add_argument("--breakdown", default=None, help="write the per-op HIP-event breakdown to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.workload is None:
         a.workload = "loco64" if a.gpus >= 8 else "loco"
     return a
@@ -192,6 +196,7 @@ class Epoch:
             self._gae_out = {}
         _, _, a32, r32 = engine.gae(self.rewards, self.values.view(T, E).double(), self.terminals, self.time_limits,
                                     last_value, 0.99, 0.95, True, out=self._gae_out)
+        self.gae_out = (a32, r32)
         ag.current_epoch = self.epoch
         atu.update_linear_schedule(ag.pf_optimizer, ag.current_epoch, ag.num_epochs, ag.plr)
         atu.update_linear_schedule(ag.vf_optimizer, ag.current_epoch, ag.num_epochs, ag.vlr)
@@ -212,6 +217,36 @@ class Epoch:
         if with_rollout:
             self.rollout()
         self.update()
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(ep, out_dir, budget=DUMP_BYTES):
+    """--dump-outputs: what the last timed step handed its caller — the rollout's actions / values / log pi_old, GAE's advantages
+    and returns, the 18 logger scalars of every minibatch update and the parameters both nets end the step with — as
+    <out_dir>/<name>.npy (float64 stays float64, everything else float32). An array that would push the total past `budget`
+    bytes is replaced by a fixed, seeded sample of its flattened elements (the same elements in every run)."""
+    arrays = {"rollout_actions": ep.acts, "rollout_values": ep.values, "gae_advantages": ep.gae_out[0],
+              "gae_returns": ep.gae_out[1], "update_stats": ep.stats[:, :18]}
+    if ep.logp is not None:
+        arrays["rollout_logp_old"] = ep.logp
+    for prefix, net in (("pf", ep.pf), ("vf", ep.vf)):
+        for k, v in net.state_dict().items():
+            arrays["%s.%s" % (prefix, k)] = v
+    os.makedirs(out_dir, exist_ok=True)
+    small = sorted(arrays, key=lambda k: arrays[k].numel())
+    left = budget - 256 * len(small)  # .npy headers
+    for i, name in enumerate(small):
+        t = arrays[name].detach()
+        a = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32, copy=False)
+        share = left // (len(small) - i)  # smallest first: what a small array leaves unused goes to the larger ones
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, max(1, share // a.itemsize), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
+    return sorted(arrays)
 
 
 def side_leg(wl_name, compute, dev, steps=3, warmup=1):
@@ -910,6 +945,9 @@ def main():
     if not stats_ok:
         raise SystemExit("bench.py: non-finite logger statistics after the timed epochs: the step is invalid")
     res["stats_finite"] = stats_ok
+    if rank == 0 and a.dump_outputs:
+        # before anything below runs the nets again (the profiled pass of roofline() updates the parameters)
+        res["dumped_outputs"] = len(dump_outputs(ep, a.dump_outputs))
     if rank == 0:
         res["roofline"] = roofline(ep, a.compute, a.breakdown)
         if res["roofline"]:

@@ -350,3 +350,31 @@ def test_header_lists_every_library_switch():
     assert read == listed, (sorted(read - listed), sorted(listed - read))
     m = re.search(r"Environment switches read by the library: (\d+)", header)
     assert int(m.group(1)) == len(read), (m.group(1), len(read))
+
+
+def test_bench_dump_outputs_names_dtypes_budget_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs on a stand-in epoch (CPU tensors): one float32 / float64 .npy per output the step hands its
+    caller, everything within the byte budget, and an array over its share sampled the same way in every run."""
+    import types
+    import bench
+    lin = torch.nn.Linear(300, 200)
+    ep = types.SimpleNamespace(acts=torch.randn(64, 6), values=torch.randn(64), logp=torch.randn(64),
+                               gae_out=(torch.randn(16, 4, dtype=torch.float64), torch.randn(16, 4, dtype=torch.float64)),
+                               stats=torch.randn(6, 24), pf=lin, vf=torch.nn.Linear(3, 1))
+    names = bench.dump_outputs(ep, str(tmp_path / "a"))
+    want = {"rollout_actions", "rollout_values", "rollout_logp_old", "gae_advantages", "gae_returns", "update_stats",
+            "pf.weight", "pf.bias", "vf.weight", "vf.bias"}
+    assert set(names) == want and sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in want)
+    load = lambda d, n: np.load(str(tmp_path / d / (n + ".npy")))
+    assert load("a", "gae_returns").dtype == np.float64 and np.array_equal(load("a", "gae_returns"), ep.gae_out[1].numpy())
+    assert load("a", "update_stats").dtype == np.float32 and np.array_equal(load("a", "update_stats"), ep.stats[:, :18].numpy())
+    assert np.array_equal(load("a", "pf.weight"), lin.weight.detach().numpy())
+    budget = 40000  # pf.weight (240 kB) must be sampled to fit
+    bench.dump_outputs(ep, str(tmp_path / "b"), budget=budget)
+    bench.dump_outputs(ep, str(tmp_path / "c"), budget=budget)
+    total = sum(os.path.getsize(str(tmp_path / "b" / f)) for f in os.listdir(tmp_path / "b"))
+    assert total <= budget, total
+    w = load("b", "pf.weight")
+    assert w.dtype == np.float32 and 0 < w.size < lin.weight.numel() and np.array_equal(w, load("c", "pf.weight"))
+    assert np.isin(w, lin.weight.detach().numpy().reshape(-1)).all()
+    assert np.array_equal(load("b", "rollout_actions"), ep.acts.numpy())

@@ -192,3 +192,51 @@ class FakeVecEnv:
 
     def close(self):
         self.closed = True
+
+
+class StandInPolicy(torch.nn.Module):
+    """Small seeded CPU policy with the collector-facing protocol of the reference's policies (explore(ob) -> {"action"}),
+    drawing its exploration noise from torch's generator: drives the collector pin (tests/test_overlay_cpu.py) and its
+    fixture (tests/golden/make_golden_overlay.py) with the same actions on both sides. Elementwise arithmetic and uniform
+    draws only (no BLAS reductions, no vectorised transcendental functions), so every machine computes the same bits."""
+
+    def __init__(self, S, A):
+        super().__init__()
+        self.A = A
+        self.w, self.b = torch.nn.Parameter(torch.rand(A) - 0.5), torch.nn.Parameter(torch.rand(A) - 0.5)
+
+    def explore(self, ob):
+        mean = (ob[:, :self.A] * self.w + self.b).clamp(-1, 1)
+        return {"action": mean + 0.3 * (torch.rand_like(mean) - 0.5)}
+
+
+class StandInValue(torch.nn.Module):
+    def __init__(self, S):
+        super().__init__()
+        self.w, self.b = torch.nn.Parameter(torch.rand(1) - 0.5), torch.nn.Parameter(torch.rand(1) - 0.5)
+
+    def forward(self, ob):
+        return ob[:, :1] * self.w + self.b
+
+
+COLLECTOR_KEYS = ["obs", "next_obs", "acts", "values", "rewards", "terminals", "time_limits"]
+
+
+def run_collector(make_collector, make_buffer, S=93, A=6, E=4, T=12):
+    """Two epochs of a collector over a deterministic vec env (terminations and max_episode_frames = 5 truncations both occur):
+    -> {buffer arrays, per-epoch train rewards, the next draw of torch's generator (its consumption)}."""
+    torch.manual_seed(3)
+    pf, vf = StandInPolicy(S, A), StandInValue(S)
+    env = FakeVecEnv(E, S, A, img=0, seed=5, p_done=0.15, time_limit_key=True)
+    buf = make_buffer(E, E * T)
+    coll = make_collector(vf, pf, env, buf, E * T)
+    torch.manual_seed(11)
+    out = {}
+    for ep in range(2):
+        r = coll.train_one_epoch()
+        out["epoch%d/train_epoch_reward" % ep] = np.array(r["train_epoch_reward"], dtype=np.float64)
+        out["epoch%d/train_rewards" % ep] = np.array(r["train_rewards"], dtype=np.float64).reshape(-1)
+    for k in COLLECTOR_KEYS:
+        out["buf/" + k] = np.asarray(getattr(buf, "_" + k))
+    out["rng_next"] = torch.rand(4).numpy()
+    return out
