@@ -327,6 +327,18 @@ int v4l_trainer_bind(v4l_trainer* tr, float* g_pf_dev, float* m_pf_dev, float* v
  * bias corrections then live on the device and advance by themselves, one per update. */
 int v4l_trainer_begin(v4l_trainer* tr, const int* rowidx_all_dev, float* stats_all_dev, double lr_pf, double lr_vf,
                       int64_t steps_done, const v4l_ppo_hyper* hp, void* stream);
+/* v4l_trainer_begin with one committed Adam step count per optimiser (step_pf / step_vf) and the opt-in guard against
+ * non-finite steps (the device-side counterpart of torch.cuda.amp.GradScaler.step). skip_all_dev: int32 [U][2] (slot 0 = pf,
+ * slot 1 = vf), or NULL = guard off (== v4l_trainer_begin with steps_done = step_pf = step_vf). With the guard on, an
+ * optimiser step of update u whose pre-clip global gradient norm is not finite is skipped — parameters and both Adam moments
+ * keep their bits and that optimiser's step count does not advance — and skip_all_dev[u][which] gets 1 (0 for a step taken).
+ * The record of a skipped update still counts its non-finite statistics (record slot 22). Whether the guard is on, and the
+ * flag address, are baked into captured graphs like the row and record addresses: keep the buffer at one address. */
+int v4l_trainer_begin_guarded(v4l_trainer* tr, const int* rowidx_all_dev, float* stats_all_dev, int* skip_all_dev, double lr_pf,
+                              double lr_vf, int64_t step_pf, int64_t step_vf, const v4l_ppo_hyper* hp, void* stream);
+/* The Adam step counts committed on the device so far (after a guarded run they may lag the number of updates, and differ
+ * from each other). Synchronises the stream. */
+int v4l_trainer_steps(v4l_trainer* tr, int64_t* step_pf_out, int64_t* step_vf_out, void* stream);
 /* The next minibatch update, == PPO.update (ppo.py:125-153). use_graph=1: the launch sequence (~20 kernels) is
  * captured once per (rollout pointers, n, hyper-parameters) as a hipGraph and replayed; needs a non-default stream.
  * The first update of a configuration always runs eagerly. */

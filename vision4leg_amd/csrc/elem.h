@@ -657,8 +657,10 @@ __device__ __forceinline__ ActorRow actor_row(const ActorArgs& p, const ActorDim
   const float clp = fminf(fmaxf(ratio, 1.f - p.clip), 1.f + p.clip) * an;
   o.lp = lp; o.ratio = ratio;
   o.sur = fminf(pre, clp);
-  // d(-mean(min(pre,clp)))/dlogp: the clipped branch has zero slope outside the clip range
-  o.dlp = (pre <= clp) ? -p.inv_n * an * ratio : 0.f;
+  // d(-mean(min(pre,clp)))/dlogp: the clipped branch has zero slope outside the clip range. Written
+  // !(pre > clp), not pre <= clp: the same for every non-NaN pair, and a NaN advantage / ratio gives a NaN slope as torch.min's
+  // backward does, instead of a silent zero that would hide it from the gradient norm (the non-finite-step guard)
+  o.dlp = !(pre > clp) ? -p.inv_n * an * ratio : 0.f;
   return o;
 }
 // the row's d(loss)/d(mean) as the backward gets it (statistics block and chain blocks: the same bits)
@@ -817,30 +819,40 @@ struct ParamSeg { float* p; int64_t goff; int64_t n; int64_t blk0; };  // blk0: 
 struct UpdCtl {
   int upd_index;        // minibatch number inside the epoch: row of rowidx_all / stats_all
   int pad0;
-  long long step;       // optimiser steps taken so far (both Adams step once per update)
+  long long step[2];    // Adam steps committed so far for [0] pf, [1] vf: both advance once per update unless a guarded run
+                        // (skip_all != null) skipped one optimiser's step — then that optimiser's count stays (GradScaler.step)
   double lr_pf, lr_vf;
   float beta1, beta2;
-  float step_size[2];   // lr / (1 - beta1^step) for [0] pf, [1] vf — refreshed by upd_begin_body (block 0 of begin_pack_kernel)
-  float bc2_sqrt;       // sqrt(1 - beta2^step)
-  float pad1;
+  float step_size[2];   // lr / (1 - beta1^(step+1)) for [0] pf, [1] vf — refreshed by upd_begin_body (block 0 of begin_pack_kernel)
+  float bc2_sqrt[2];    // sqrt(1 - beta2^(step+1)), per optimiser
 };
-__global__ void ctl_set_kernel(UpdCtl* c, int upd_index, long long step, double lr_pf, double lr_vf, float b1, float b2) {
-  c->upd_index = upd_index; c->step = step; c->lr_pf = lr_pf; c->lr_vf = lr_vf; c->beta1 = b1; c->beta2 = b2;
+static_assert(sizeof(UpdCtl) <= 256, "UpdCtl must fit in front of stats_cur (control buffer layout [UpdCtl | stats_cur | rowidx_cur])");
+__global__ void ctl_set_kernel(UpdCtl* c, int upd_index, long long step_pf, long long step_vf, double lr_pf, double lr_vf, float b1,
+                               float b2) {
+  c->upd_index = upd_index; c->step[0] = step_pf; c->step[1] = step_vf; c->lr_pf = lr_pf; c->lr_vf = lr_vf; c->beta1 = b1; c->beta2 = b2;
 }
-// the Adam step / bias corrections of the update being opened (double precision, like torch/optim/adam.py::_single_tensor_adam)
+// the candidate Adam step sizes / bias corrections of the update being opened, from the committed counts + 1 (double precision,
+// like torch/optim/adam.py::_single_tensor_adam). Nothing is committed here: block 0 of each optimiser's clip_adam_kernel
+// advances that optimiser's count when its step is taken.
 __device__ __forceinline__ void upd_begin_step(UpdCtl* c) {
   if (threadIdx.x == 0) {
-    const long long step = c->step + 1;
-    c->step = step;
-    const double bc1 = 1.0 - pow((double)c->beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)c->beta2, (double)step);
+    const long long s0 = c->step[0] + 1, s1 = c->step[1] + 1;
+    const double b1 = (double)c->beta1, b2 = (double)c->beta2;
+    const double bc1 = 1.0 - pow(b1, (double)s0);
+    const double bc2 = 1.0 - pow(b2, (double)s0);
     c->step_size[0] = (float)(c->lr_pf / bc1);
-    c->step_size[1] = (float)(c->lr_vf / bc1);
-    c->bc2_sqrt = (float)sqrt(bc2);
+    c->bc2_sqrt[0] = (float)sqrt(bc2);
+    if (s1 == s0) {  // the counts agree (always, unless a guarded run skipped a step): one pair of pow()s
+      c->step_size[1] = (float)(c->lr_vf / bc1);
+      c->bc2_sqrt[1] = c->bc2_sqrt[0];
+    } else {
+      c->step_size[1] = (float)(c->lr_vf / (1.0 - pow(b1, (double)s1)));
+      c->bc2_sqrt[1] = (float)sqrt(1.0 - pow(b2, (double)s1));
+    }
   }
 }
 // Opens update #upd_index: selects its rows (identity when rowidx_all is null), clears the statistics record and
-// advances the Adam step / bias corrections.
+// computes the candidate Adam step sizes / bias corrections.
 // adv != null: also the advantage statistics of the selected rows (adv_stats_kernel's work, one launch less).
 __device__ __forceinline__ void upd_begin_body(UpdCtl* c, const int* __restrict__ rowidx_all, int n, int* rowidx_cur,
                                                float* stats_cur, const float* __restrict__ adv) {
@@ -880,12 +892,12 @@ __device__ __forceinline__ void upd_begin_body(UpdCtl* c, const int* __restrict_
 __global__ __launch_bounds__(256) void clip_adam_kernel(const ParamSeg* __restrict__ segs, int nseg,
                                                         const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, const float* __restrict__ part, int npart,
-                                                        const float* __restrict__ extra, int nextra, float max_norm, float eps, const UpdCtl* __restrict__ ctl,
+                                                        const float* __restrict__ extra, int nextra, float max_norm, float eps, UpdCtl* ctl,
                                                         int which, float* __restrict__ norm_out, UpdCtl* close_ctl,
-                                                        const float* stats_cur, float* __restrict__ stats_all) {
+                                                        const float* stats_cur, float* __restrict__ stats_all, int* __restrict__ skip_all) {
   const ParamSeg sg = segs[find_desc(segs, nseg, (int64_t)blockIdx.x)];
   const float beta1 = ctl->beta1, beta2 = ctl->beta2;
-  const float step_size = ctl->step_size[which], bc2_sqrt = ctl->bc2_sqrt;
+  const float step_size = ctl->step_size[which], bc2_sqrt = ctl->bc2_sqrt[which];
   const int lane_ = threadIdx.x & 63;
   // this thread's element: its four operands are requested before the norm is summed (they do not depend on it; behind the
   // barrier below they would be one more round trip at the end of the block's chain — round 5)
@@ -912,6 +924,15 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const ParamSeg* __restri
   const float tot = sqrtf((wpart[0] + wpart[1]) + (wpart[2] + wpart[3]));
   const float coef = fminf(max_norm / (tot + 1e-6f), 1.f);
   if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out != nullptr) *norm_out = tot;
+  // skip_all != null (the opt-in guard): a step whose pre-clip norm is not finite writes nothing and does not count. Every block
+  // summed the same partials in the same order, so every block takes the same decision without a grid-wide sync (data parallel:
+  // the partials are those of the all-reduced bucket, so every rank skips the same steps).
+  const bool skip = skip_all != nullptr && !(fabsf(tot) <= 3.0e38f);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (!skip) ctl->step[which] = ctl->step[which] + 1;  // commit this optimiser's Adam step
+    // (the update index before the closing block below advances it: program order of this thread)
+    if (skip_all != nullptr) skip_all[(int64_t)ctl->upd_index * 2 + which] = skip ? 1 : 0;
+  }
   if (blockIdx.x == 0 && close_ctl != nullptr) {
     // last launch of an update: publish the statistics record (this block just completed it with the policy's gradient
     // norm) and move on to the next minibatch (no separate closing launch)
@@ -927,7 +948,7 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const ParamSeg* __restri
     __syncthreads();
     if (threadIdx.x == 0) close_ctl->upd_index = u + 1;
   }
-  if (!mine) return;
+  if (!mine || skip) return;
   const float gr = g_in * coef;
   float mm = m_in, vv = v_in;
   mm = mm + (gr - mm) * (1.f - beta1);           // exp_avg.lerp_(grad, 1 - beta1)

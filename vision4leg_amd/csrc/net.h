@@ -206,6 +206,7 @@ struct v4l_trainer {
   int n_max = 0;
   const int* rowidx_all = nullptr;
   float* stats_all = nullptr;
+  int* skip_all = nullptr;  // [U][2] skipped-step flags of a guarded run (v4l_trainer_begin_guarded); null: the guard is off
   hipStream_t aux = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // hipGraph of one minibatch update

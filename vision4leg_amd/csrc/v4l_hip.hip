@@ -2788,7 +2788,7 @@ static int launch_actor_loss_heads(hipStream_t s, const ActorArgs& aa, const Row
 extern "C" {
 
 const char* v4l_last_error(void) { return v4l::last_error(); }
-int v4l_version(void) { return 106; }  // round 6: V4L_F16 compute mode, v4l_net_grad_scale, record slot 23; v4l_actor_step_rows / v4l_host_cast_rows
+int v4l_version(void) { return 107; }  // per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
 int v4l_abi_sizeof(int which) {
   return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) : -1;
 }
@@ -3511,15 +3511,31 @@ int v4l_trainer_bind(v4l_trainer* tr, float* g_pf_dev, float* m_pf_dev, float* v
   return 0;
 }
 
-int v4l_trainer_begin(v4l_trainer* tr, const int* rowidx_all_dev, float* stats_all_dev, double lr_pf, double lr_vf,
-                      int64_t steps_done, const v4l_ppo_hyper* hp, void* stream) {
-  V4L_REQUIRE(tr && tr->bound && hp && steps_done >= 0, "v4l_trainer_begin: bad argument");
-  if (rowidx_all_dev != tr->rowidx_all || stats_all_dev != tr->stats_all) drop_graph(tr);  // baked into the graph
+int v4l_trainer_begin_guarded(v4l_trainer* tr, const int* rowidx_all_dev, float* stats_all_dev, int* skip_all_dev, double lr_pf,
+                              double lr_vf, int64_t step_pf, int64_t step_vf, const v4l_ppo_hyper* hp, void* stream) {
+  V4L_REQUIRE(tr && tr->bound && hp && step_pf >= 0 && step_vf >= 0, "v4l_trainer_begin: bad argument");
+  // baked into the graph (the flag pointer also decides whether the guard is on)
+  if (rowidx_all_dev != tr->rowidx_all || stats_all_dev != tr->stats_all || skip_all_dev != tr->skip_all) drop_graph(tr);
   tr->rowidx_all = rowidx_all_dev;
   tr->stats_all = stats_all_dev;
-  hipLaunchKernelGGL(ctl_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, tr->ctl, 0, (long long)steps_done, lr_pf,
-                     lr_vf, hp->beta1, hp->beta2);
+  tr->skip_all = skip_all_dev;
+  hipLaunchKernelGGL(ctl_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, tr->ctl, 0, (long long)step_pf, (long long)step_vf,
+                     lr_pf, lr_vf, hp->beta1, hp->beta2);
   V4L_LAUNCH_CHECK();
+  return 0;
+}
+int v4l_trainer_begin(v4l_trainer* tr, const int* rowidx_all_dev, float* stats_all_dev, double lr_pf, double lr_vf,
+                      int64_t steps_done, const v4l_ppo_hyper* hp, void* stream) {
+  return v4l_trainer_begin_guarded(tr, rowidx_all_dev, stats_all_dev, nullptr, lr_pf, lr_vf, steps_done, steps_done, hp, stream);
+}
+int v4l_trainer_steps(v4l_trainer* tr, int64_t* step_pf_out, int64_t* step_vf_out, void* stream) {
+  V4L_REQUIRE(tr && tr->bound && step_pf_out && step_vf_out, "v4l_trainer_steps: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  long long st[2] = {0, 0};
+  V4L_HIP_CHECK(hipMemcpyAsync(st, tr->ctl->step, sizeof(st), hipMemcpyDeviceToHost, s));
+  V4L_HIP_CHECK(hipStreamSynchronize(s));
+  *step_pf_out = st[0];
+  *step_vf_out = st[1];
   return 0;
 }
 
@@ -3647,7 +3663,7 @@ static int adam_step(v4l_trainer* tr, v4l_net* net, float* g, float* m, float* v
   }
   V4L_KLAUNCH("clip_adam", 0, s, clip_adam_kernel, dim3((unsigned)net->seg_blocks), dim3(256), 0, s, net->d_segs,
               (int)net->params.size(), g, m, v, part, gb, extra, nextra, hp->max_grad_norm, hp->eps, tr->ctl, which, norm_out,
-              close_update ? tr->ctl : (UpdCtl*)nullptr, (const float*)tr->stats_cur, tr->stats_all);
+              close_update ? tr->ctl : (UpdCtl*)nullptr, (const float*)tr->stats_cur, tr->stats_all, tr->skip_all);
   V4L_LAUNCH_CHECK();
   return 0;
 }

@@ -80,7 +80,8 @@ __device__ __forceinline__ ActorRow fb_actor_row(const ActorArgs& p, const Actor
   const float clp = fminf(fmaxf(ratio, 1.f - p.clip), 1.f + p.clip) * an;
   o.lp = lp; o.ratio = ratio;
   o.sur = fminf(pre, clp);
-  o.dlp = (pre <= clp) ? -p.inv_n * an * ratio : 0.f;
+  // (!(pre > clp): NaN-propagating like actor_row in elem.h)
+  o.dlp = !(pre > clp) ? -p.inv_n * an * ratio : 0.f;
   return o;
 }
 

@@ -372,7 +372,10 @@ class HipTrainer:
     self._alloc_ws(batch)
     self.hp = PPOHyper(clip_para, entropy_coeff, max_grad_norm, betas[0], betas[1], eps,
                        int(bool(clipped_value_loss)), int(world_size))
-    self.step = 0  # Adam steps taken (both optimisers step once per update)
+    self.step = 0  # minibatch updates run (== both Adam step counts while no guarded step was skipped)
+    self._adam_steps = (0, 0)  # committed Adam step counts (pf, vf) as last known on the host
+    self._guarded = False  # the open run skips non-finite optimiser steps (begin(..., skip_all=...))
+    self._steps_on_device = False  # a guarded run has updated: the device holds the current counts
     self._one_stats = torch.zeros(V4L_STATS, dtype=torch.float32, device=dev)
     self.has_comm = False
 
@@ -467,17 +470,44 @@ class HipTrainer:
     for net in (self.pf, self.vf):
       net.mark_dirty()
 
-  def begin(self, rowidx_all, stats_all, lr_pf, lr_vf):
-    """Open a run of updates on rows rowidx_all[u] (int32 [U][n] device tensor or None) -> stats_all[u]."""
-    self._run = (rowidx_all, stats_all)  # keep alive
-    check(self.L.v4l_trainer_begin(self.h, _ptr(rowidx_all), _ptr(stats_all), float(lr_pf), float(lr_vf), self.step,
-                                   C.byref(self.hp), _stream()), "v4l_trainer_begin")
+  def begin(self, rowidx_all, stats_all, lr_pf, lr_vf, skip_all=None):
+    """Open a run of updates on rows rowidx_all[u] (int32 [U][n] device tensor or None) -> stats_all[u].
+    skip_all: int32 [U][2] device tensor (slot 0 = pf, 1 = vf) turns on the guard for this run: an optimiser step whose
+    gradient norm is not finite is skipped (no write, no Adam step counted) and flagged there. Keep it at one address from run
+    to run: the captured graph is keyed on it, like the row and record addresses."""
+    spf, svf = self.adam_steps()
+    self._run = (rowidx_all, stats_all, skip_all)  # keep alive
+    self._guarded = skip_all is not None
+    if not self._guarded and spf == svf:
+      check(self.L.v4l_trainer_begin(self.h, _ptr(rowidx_all), _ptr(stats_all), float(lr_pf), float(lr_vf), spf,
+                                     C.byref(self.hp), _stream()), "v4l_trainer_begin")
+    else:
+      check(self.L.v4l_trainer_begin_guarded(self.h, _ptr(rowidx_all), _ptr(stats_all), _ptr(skip_all), float(lr_pf),
+                                             float(lr_vf), spf, svf, C.byref(self.hp), _stream()), "v4l_trainer_begin_guarded")
+
+  def adam_steps(self):
+    """(pf, vf) Adam step counts committed so far. After a guarded run they are read back from the device (a sync); otherwise
+    both equal the number of updates run."""
+    if self._steps_on_device:
+      torch.cuda.synchronize(self.device)
+      spf, svf = C.c_int64(0), C.c_int64(0)
+      check(self.L.v4l_trainer_steps(self.h, C.byref(spf), C.byref(svf), _stream()), "v4l_trainer_steps")
+      self._adam_steps = (spf.value, svf.value)
+      self._steps_on_device = False
+    return self._adam_steps
+
+  def _count(self, updates):
+    self.step += updates
+    if self._guarded:
+      self._steps_on_device = True
+    else:
+      self._adam_steps = (self._adam_steps[0] + updates, self._adam_steps[1] + updates)
 
   def update_next(self, ro, n, graph=True):
     self._pre(n)
     check(self.L.v4l_trainer_update_next(self.h, C.byref(ro), n, C.byref(self.hp), int(graph), _stream()),
           "v4l_trainer_update_next")
-    self.step += 1
+    self._count(1)
     self._after_steps()
 
   def update_run(self, ro, n, count, graph=True):
@@ -485,13 +515,14 @@ class HipTrainer:
     self._pre(n)
     check(self.L.v4l_trainer_update_run(self.h, C.byref(ro), n, C.byref(self.hp), int(count), int(graph), _stream()),
           "v4l_trainer_update_run")
-    self.step += int(count)
+    self._count(int(count))
     self._after_steps()
 
-  def update(self, ro, rowidx, n, lr_pf, lr_vf, stats):
-    """One eager PPO.update on minibatch rows rowidx (int32 device tensor or None); stats: [V4L_STATS] floats."""
+  def update(self, ro, rowidx, n, lr_pf, lr_vf, stats, skip=None):
+    """One eager PPO.update on minibatch rows rowidx (int32 device tensor or None); stats: [V4L_STATS] floats; skip: None, or
+    int32 [1][2] flags (the guard, see begin)."""
     self._pre(n)
-    self.begin(rowidx, stats, lr_pf, lr_vf)
+    self.begin(rowidx, stats, lr_pf, lr_vf, skip)
     self.update_next(ro, n, graph=False)
 
   # phases, for the data-parallel schedule (all-reduce between grads and step); begin() first
@@ -515,7 +546,7 @@ class HipTrainer:
 
   def actor_step(self):
     check(self.L.v4l_trainer_actor_step(self.h, C.byref(self.hp), _stream()), "v4l_trainer_actor_step")
-    self.step += 1
+    self._count(1)
     self._after_steps()
 
 

@@ -109,11 +109,29 @@ def device_identity(device):
     return int.from_bytes(hashlib.sha1(repr(ident).encode()).digest()[:8], "little") >> 1
 
 
+def _check_update_records(stats, flags, guarded, label=lambda u: "minibatch update %d" % u):
+    """The host's rule for the statistics records of a run of updates. stats: [U][V4L_STATS] floats; flags: [U][2] int32
+    skipped-step flags (slot 0 = pf, 1 = vf) or None; guarded: the run skipped non-finite optimiser steps
+    (PPO(skip_nonfinite_steps=True)). Raises FloatingPointError for the first update whose record counts non-finite statistics
+    (slot ST_NONFINITE) unless — guarded only — one of its optimiser steps was skipped; a non-finite ratio next to finite
+    gradients still raises. -> (skipped pf steps, skipped vf steps)."""
+    stats = np.asarray(stats)
+    skipped = np.zeros((len(stats), 2), dtype=np.int64)
+    if guarded:
+        skipped = np.asarray(flags, dtype=np.int64).reshape(len(stats), 2) != 0
+    bad = np.nonzero((stats[:, _lib.ST_NONFINITE] > 0) & ~skipped.any(axis=1))[0]
+    if len(bad):  # the device-side tripwire (collector/on_policy.py:102-107 "NaN detected. BOOM")
+        raise FloatingPointError("vision4leg_amd: non-finite training statistics in %s: %s"
+                                 % (label(int(bad[0])), {k: float(stats[bad[0], j]) for j, k in enumerate(_lib.STAT_KEYS)}))
+    return int(skipped[:, 0].sum()), int(skipped[:, 1].sum())
+
+
 class PPO:
     def __init__(self, pf, vf, plr=3e-4, vlr=3e-4, optimizer_class=None, entropy_coeff=0.001, clip_para=0.2,
                  opt_epochs=10, clipped_value_loss=False, shuffle=True, tau=None, gae=True, env=None,
                  replay_buffer=None, collector=None, logger=None, grad_clip=None, discount=0.99, num_epochs=3000,
-                 batch_size=128, device="cpu", save_interval=100, eval_interval=1, save_dir=None, **kwargs):
+                 batch_size=128, device="cpu", save_interval=100, eval_interval=1, save_dir=None, skip_nonfinite_steps=False,
+                 **kwargs):
         if optimizer_class is not None and optimizer_class is not torch.optim.Adam:
             raise NotImplementedError("vision4leg_amd: PPO runs Adam on the HIP engine; optimizer_class must be Adam")
         self.device = torch.device(device)
@@ -159,6 +177,11 @@ class PPO:
         self.clipped_value_loss = clipped_value_loss
         self.sample_key = ["obs", "acts", "advs", "estimate_returns", "values"]
         self.current_epoch = 0
+        # opt-in (config "skip_nonfinite_steps": true): an optimiser step whose gradient norm is not finite is skipped on the
+        # device — parameters, Adam moments and that optimiser's step count untouched, like torch.cuda.amp.GradScaler.step —
+        # instead of writing NaN and raising after the epoch. Off (the reference's behaviour): step, then raise.
+        self.skip_nonfinite_steps = bool(skip_nonfinite_steps)
+        self.skipped_steps = {"pf": 0, "vf": 0}
         # ---- engine
         self.world_size = _dist_world()
         # the data-parallel update (four phases + one all-reduce per optimiser step) also runs on a 1-rank process group
@@ -358,17 +381,38 @@ class PPO:
             for b in buf.one_iteration(self.batch_size, self.sample_key, self.shuffle):
                 batches.append(b["rowidx"])
         rowidx = torch.from_numpy(np.stack(batches)).to(self.device)  # one upload per epoch
-        stats = torch.zeros(len(batches), _lib.V4L_STATS, dtype=torch.float32, device=self.device)
+        U = len(batches)
+        stats = torch.zeros(U, _lib.V4L_STATS, dtype=torch.float32, device=self.device)
         self.run_updates(ro, rowidx, stats)
-        host = stats.cpu().numpy()  # the only device->host sync of the epoch's updates
-        bad = np.nonzero(host[:, _lib.ST_NONFINITE] > 0)[0]
-        if len(bad):  # the device-side tripwire (collector/on_policy.py:102-107 "NaN detected. BOOM")
-            raise FloatingPointError("vision4leg_amd: non-finite training statistics in minibatch update %d of epoch %d: %s"
-                                     % (int(bad[0]), self.current_epoch,
-                                        {k: float(host[bad[0], j]) for j, k in enumerate(_lib.STAT_KEYS)}))
+        flags = None
+        if self.skip_nonfinite_steps:  # records and flags share one allocation: still one device->host copy
+            rec = self._rec_buf.cpu()
+            host = rec[:U * _lib.V4L_STATS].view(U, _lib.V4L_STATS).numpy()
+            flags = rec[U * _lib.V4L_STATS:].view(torch.int32).view(U, 2).numpy()
+        else:
+            host = stats.cpu().numpy()  # the only device->host sync of the epoch's updates
+        spf, svf = _check_update_records(host, flags, self.skip_nonfinite_steps,
+                                         lambda u: "minibatch update %d of epoch %d" % (u, self.current_epoch))
+        self._note_skipped(spf, svf)
         self._note_f16_saturation(float(host[:, _lib.ST_F16_SAT].sum()))
-        for row in host:
-            self.logger.add_update_info({k: float(row[j]) for j, k in enumerate(_lib.STAT_KEYS)})
+        for u, row in enumerate(host):
+            self.logger.add_update_info(self._info(row, None if flags is None else flags[u]))
+
+    def _info(self, row, flags):
+        """The logger's info dict of one update: the 18 reference keys, and with the guard on skipped/pf and skipped/vf (0 / 1)."""
+        info = {k: float(row[j]) for j, k in enumerate(_lib.STAT_KEYS)}
+        if flags is not None:
+            info["skipped/pf"], info["skipped/vf"] = int(flags[0] != 0), int(flags[1] != 0)
+        return info
+
+    def _note_skipped(self, spf, svf):
+        if spf or svf:
+            import warnings
+            self.skipped_steps["pf"] += spf
+            self.skipped_steps["vf"] += svf
+            warnings.warn("vision4leg_amd: skipped %d policy and %d critic optimiser step(s) whose gradient norm was not finite "
+                          "(epoch %d; PPO.skipped_steps keeps the totals: %s)" % (spf, svf, self.current_epoch, self.skipped_steps),
+                          RuntimeWarning)
 
     f16_saturated = 0.0  # V4L_COMPUTE=f16: loss-gradient elements clamped at +-V4L_F16_GRAD_CLAMP so far (include/v4l_hip.h, record slot 23)
 
@@ -383,8 +427,9 @@ class PPO:
                               "want V4L_COMPUTE=bf16." % (int(count), 32768.0, _lib.ST_F16_SAT), RuntimeWarning)
             self.f16_saturated += count
 
-    def run_updates(self, ro, rowidx, stats):
-        """All minibatch updates of an epoch: rowidx [U][n] int32 (device), stats [U][V4L_STATS] (device).
+    def run_updates(self, ro, rowidx, stats, skip=None):
+        """All minibatch updates of an epoch: rowidx [U][n] int32 (device), stats [U][V4L_STATS] (device); skip: None or an
+        int32 [U][2] device tensor that receives the guard's skipped-step flags (skip_nonfinite_steps).
         The whole run is ONE hipGraph replay on the trainer's stream (round 6; one replay per update with V4L_EPOCH_GRAPH=0) — on one
         GPU, and data-parallel with the library's own communicator (V4L_DP_COMM=rccl: both all-reduces are nodes of that graph). With torch.distributed doing the exchange
         (the data-parallel default) an update is four eager phases with one all-reduce per optimiser step between them."""
@@ -393,12 +438,16 @@ class PPO:
         # the captured graph is keyed on these addresses: keep them stable from epoch to epoch
         if getattr(self, "_rowidx_buf", None) is None or self._rowidx_buf.shape != rowidx.shape:
             self._rowidx_buf = torch.empty_like(rowidx)
-            self._stats_buf = torch.zeros(U, _lib.V4L_STATS, dtype=torch.float32, device=self.device)
+            # [U][V4L_STATS] records, then the guard's [U][2] int32 skipped-step flags in the same allocation
+            self._rec_buf = torch.zeros(U * (_lib.V4L_STATS + 2), dtype=torch.float32, device=self.device)
+            self._stats_buf = self._rec_buf[:U * _lib.V4L_STATS].view(U, _lib.V4L_STATS)
+            self._skip_buf = self._rec_buf[U * _lib.V4L_STATS:].view(torch.int32).view(U, 2)
         self._rowidx_buf.copy_(rowidx)
         cur = torch.cuda.current_stream(self.device)
         tr.stream.wait_stream(cur)
         with torch.cuda.stream(tr.stream):
-            tr.begin(self._rowidx_buf, self._stats_buf, self.pf_optimizer.lr, self.vf_optimizer.lr)
+            tr.begin(self._rowidx_buf, self._stats_buf, self.pf_optimizer.lr, self.vf_optimizer.lr,
+                     self._skip_buf if self.skip_nonfinite_steps else None)
             if not self.dp_phases and self.use_graph and os.environ.get("V4L_EPOCH_GRAPH", "1") != "0":
                 # the whole epoch loop (ppo.py:28-40) as ONE hipGraph replay (round 6); V4L_EPOCH_GRAPH=0: one replay per update
                 self.training_update_num += U
@@ -411,11 +460,13 @@ class PPO:
                     else:
                         self._update_phases(ro, n)
             stats.copy_(self._stats_buf)
+            if skip is not None:
+                skip.copy_(self._skip_buf)
         cur.wait_stream(tr.stream)
 
     def _update_phases(self, ro, n):
         """The exchange done by torch.distributed (V4L_DP_COMM=torch): four eager phases, the buckets [gradients | tail]
-        all-reduced between them."""
+        all-reduced between them. (The guard's decision is taken on the all-reduced buckets: every rank skips the same steps.)"""
         dist = torch.distributed
         tr = self.trainer
         tr.critic_grads(ro, n)
@@ -450,19 +501,22 @@ class PPO:
             vals = up(batch["values"]).reshape(n)
             ro = HipTrainer.rollout(self._stage[0], self._stage[1], acts, advs, rets, vals)
             stats = torch.zeros(1, _lib.V4L_STATS, dtype=torch.float32, device=dev)
+            skip = torch.zeros(1, 2, dtype=torch.int32, device=dev) if self.skip_nonfinite_steps else None
             tr = self.trainer
             if not self.dp_phases:
-                tr.update(ro, None, n, self.pf_optimizer.lr, self.vf_optimizer.lr, stats)
+                tr.update(ro, None, n, self.pf_optimizer.lr, self.vf_optimizer.lr, stats, skip)
             else:
                 tr._pre(n)
-                tr.begin(None, stats, self.pf_optimizer.lr, self.vf_optimizer.lr)
+                tr.begin(None, stats, self.pf_optimizer.lr, self.vf_optimizer.lr, skip)
                 self._update_phases(ro, n)
             host = stats[0].cpu().numpy()
-        if host[_lib.ST_NONFINITE] > 0:  # the device-side tripwire, as in _update_epoch_resident
-            raise FloatingPointError("vision4leg_amd: non-finite training statistics in minibatch update %d: %s"
-                                     % (self.training_update_num, {k: float(host[j]) for j, k in enumerate(_lib.STAT_KEYS)}))
+            flags = skip.cpu().numpy() if skip is not None else None
+        # the device-side tripwire, as in _update_epoch_resident
+        spf, svf = _check_update_records(host[None], flags, self.skip_nonfinite_steps,
+                                         lambda u: "minibatch update %d" % self.training_update_num)
+        self._note_skipped(spf, svf)
         self._note_f16_saturation(float(host[_lib.ST_F16_SAT]))
-        return {k: float(host[j]) for j, k in enumerate(_lib.STAT_KEYS)}
+        return self._info(host, None if flags is None else flags[0])
 
     # ---- outer loop (rl_algo.py:97-168) ----------------------------------------------------------------
     def train(self):
