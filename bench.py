@@ -10,8 +10,10 @@ on a synthetic epoch (distributions of BASELINE.md §3) that is resident in HBM 
 value = E*T*n_gpus / t_step. Multi-GPU: one process per GPU (torchrun), each rank owns an env shard (weak scaling),
 gradients cross ranks with one RCCL all-reduce per optimiser step.
 
-Prints ONE JSON line on rank 0. Extra objects: "roofline" (dominant kernel, from HIP-event timings collected by the
-library's built-in profiler on the launch stream) and "cpu_baseline" (the CPU oracle on a bounded sample).
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.
+--full then measures the rest, each after the timed region: "roofline" (dominant kernel, from HIP-event timings collected
+by the library's built-in profiler on the launch stream over one extra step), "cpu_baseline" (the CPU oracle on a bounded
+sample), parity checks, the other compute modes, option variants and the transfer / protocol legs.
 """
 import argparse
 import json
@@ -92,16 +94,23 @@ def parse(argv=None):
                     help="default: by --gpus — 1, 2, 4 GPUs: loco (BASELINE configs[2] / [3]: 32 envs per GPU); 8 GPUs: loco64 "
                          "(configs[4]: 64 envs per GPU)")
     ap.add_argument("--compute", default=os.environ.get("V4L_COMPUTE", "f16"), choices=["bf16", "f16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle parity check, h2d and reference-protocol legs")
-    ap.add_argument("--no-reference-protocol", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the line can report: roofline (one profiled extra "
+                         "step), parity checks, the other compute modes, option variants, the 1-rank DP leg, h2d / reference-"
+                         "protocol / collector legs, the CPU baseline, batch-1 latency. Default: the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="with --full: skip the oracle parity check, h2d and reference-protocol legs")
+    ap.add_argument("--no-reference-protocol", action="store_true", help="with --full: skip the reference-protocol leg")
     ap.add_argument("--no-rollout", action="store_true", help="time (ii)-(iv) only (the reference's Train___Time)")
-    ap.add_argument("--breakdown", default=None, help="write the per-op HIP-event breakdown to this file")
+    ap.add_argument("--breakdown", default=None, help="with --full: write the per-op HIP-event breakdown to this file")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
     a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if a.breakdown and not a.full:
+        ap.error("--breakdown needs --full (the breakdown comes from the roofline's profiled step)")
     if a.workload is None:
         a.workload = "loco64" if a.gpus >= 8 else "loco"
     return a
@@ -292,8 +301,9 @@ def dp1_ingraph_leg(workload, compute):
     schedule visible in the single-GPU line, and times one all-reduce call (world 1: its launch / completion floor)."""
     env = dict(os.environ, V4L_FORCE_DP_PHASES="1", V4L_BENCH_CHILD="1", V4L_COMPUTE=compute)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None); env.pop("MASTER_PORT", None)
+    # --full: the all-reduce time this leg reports comes from the child's roofline pass
     cmd = launcher_argv(1, ["--gpus", "1", "--workload", workload, "--compute", compute, "--steps", "3", "--warmup", "1",
-                            "--no-parity", "--no-cpu-baseline"])
+                            "--full", "--no-parity", "--no-cpu-baseline"])
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -948,72 +958,73 @@ def main():
     if rank == 0 and a.dump_outputs:
         # before anything below runs the nets again (the profiled pass of roofline() updates the parameters)
         res["dumped_outputs"] = len(dump_outputs(ep, a.dump_outputs))
-    if rank == 0:
-        res["roofline"] = roofline(ep, a.compute, a.breakdown)
-        if res["roofline"]:
-            n_upd_epoch = OPT_EPOCHS * (wl["E"] * wl["T"] // wl["B"])
-            # wall clock of one update inside the timed region (graph replays incl. host gaps): (epoch - rollout) / updates
-            res["roofline"]["update_us"] = round(1e6 * (dt - t_roll) / (a.steps * n_upd_epoch), 1)
-        upd_per_epoch = OPT_EPOCHS * (wl["E"] * wl["T"] // wl["B"])
-        bucket = 4 * (int(ep.vf.hip.total_params) + 8)
-        if dist_on:
-            res["allreduce"] = LAST_ALLREDUCE
-            if world > 1:
-                # prediction from THIS run's own compute time: strip the measured collectives, add the modelled ones
-                ar_ms = (LAST_ALLREDUCE["us_per_call"] * 2 * upd_per_epoch * 1e-3) if LAST_ALLREDUCE else 0.0
-                res["dp_model"] = dp_model(world, bucket, 12.0, None, max(1e3 * dt / a.steps - ar_ms, 1e-3), upd_per_epoch,
-                                           wl["E"] * wl["T"])
-                res["dp_model"]["allreduce_us_measured"] = LAST_ALLREDUCE["us_per_call"] if LAST_ALLREDUCE else None
-        child = os.environ.get("V4L_BENCH_CHILD", "0") != "0"
-        if world == 1 and not a.no_parity and not child and a.workload in ("loco", "loco64"):
-            # side legs (driver-visible, all after the timed region): the other two compute modes with the same parity check, the DP
-            # schedule on one rank, the net's option variants (max_pool; token_norm, use_pytorch_encoder), and the multi-GPU cost model
-            notes = {"f32": "compute=f32: exact-fp32 MFMA (v_mfma_f32_16x16x4_f32) — the mode whose outputs meet the north star's "
-                            "1e-3 against the fp32 reference literally in every case (DESIGN.md section 2)",
-                     "f16": "compute=f16: IEEE half operands (v_mfma_f32_16x16x32_f16), fp32 accumulate, loss-gradient rows scaled by a "
-                            "power of two — bf16's speed, ~8 x closer to the fp32 reference (DESIGN.md section 2)",
-                     "bf16": "compute=bf16: bf16 operands (v_mfma_f32_16x16x32_bf16), fp32 accumulate"}
-            for other in ("f32", "f16", "bf16"):
-                if other != a.compute:
-                    res[other + "_mode"] = dict(side_leg(a.workload, other, dev), parity_check=parity_check(wl, other, dev),
-                                                note=notes[other])
-                    res[other + "_mode_value"] = res[other + "_mode"]["value"]  # flat: the driver's parser drops nested objects
-                else:
-                    res[other + "_mode_value"] = value  # the headline's own mode, under the same flat name as the side legs
-            res["dp1_ingraph"] = dp1_ingraph_leg(a.workload, a.compute)
-            res["dp1_ingraph_value"] = res["dp1_ingraph"].get("value")
-            res["option_variant"] = side_leg("loco_max", a.compute, dev, steps=2, warmup=1)
-            # (round 5: the other two net options, fused since this round — DESIGN.md section 1)
-            res["option_variants"] = {w: side_leg(w, a.compute, dev, steps=2, warmup=1) for w in ("loco_tn", "loco_pe")}
-            alpha0 = (res["dp1_ingraph"].get("allreduce") or {}).get("us_per_call") or 12.0
-            res["dp_model"] = {str(n): dp_model(n, bucket, alpha0, None, 1e3 * dt / a.steps, upd_per_epoch, wl["E"] * wl["T"])
-                               for n in (2, 4, 8)}
-        if world == 1 and not a.no_parity:
-            res["parity_check"] = parity_check(wl, a.compute, dev)
-            res["h2d_ms_per_step"] = round(h2d_per_step(wl, dev), 4)
-            res["h2d_note"] = ("pinned upload of E x (S+16384) fp32 observation rows per env step, NOT inside `value` (the "
-                               "epoch is resident in HBM when the timed region starts); value_incl_h2d adds T x this, unoverlapped")
-            res["value_incl_h2d"] = round(frames * a.steps / (dt + a.steps * wl["T"] * res["h2d_ms_per_step"] * 1e-3), 1)
-            if not a.no_rollout and not a.no_reference_protocol:
-                res["reference_protocol"] = reference_protocol(wl, a.compute, dev)
-            if not a.no_rollout and ep.actor is not None:
-                # the headline WITH the critical-path transfers: the product's collector over a zero-cost env
-                res["fast_collector"] = fast_collector(wl, a.compute, dev)
-                res["value_incl_transfers"] = res["fast_collector"]["value"]
-                res["value_incl_transfers_ratio"] = round(res["value_incl_transfers"] / value, 3)
-                res["value_incl_transfers_note"] = (
-                    "`value` starts with the epoch resident in HBM (the contract); value_incl_transfers is the same epoch "
-                    "driven by VecOnPolicyCollector from float64 host rows: per env step a host cast, %d bytes read over PCIe by the kernels, "
-                    "2 launches and the action's D2H, serialised by the synchronous vec-env protocol"
-                    % res["fast_collector"]["h2d_bytes_per_env_step"])
-        if not a.no_cpu_baseline and world == 1:  # the host baseline is an N = 1 measurement (the other ranks would idle)
-            res["cpu_baseline"] = cpu_baseline(wl, a.compute)
-            res["vs_cpu_baseline"] = round(value / world / res["cpu_baseline"]["value"], 1)
-        if world == 1 and ep.actor is not None:
-            import vision4leg_amd.torchrl.policies as policies
-            res["batch1_inference"] = batch1_latency(ep, policies, dev)
-    elif dist_on:
-        ep.update()  # keep collectives matched with rank 0's profiled pass
+    if a.full:  # the legs that take runs of their own (profiled step, side legs, CPU baseline); a plain run skips them
+        if rank == 0:
+            res["roofline"] = roofline(ep, a.compute, a.breakdown)
+            if res["roofline"]:
+                n_upd_epoch = OPT_EPOCHS * (wl["E"] * wl["T"] // wl["B"])
+                # wall clock of one update inside the timed region (graph replays incl. host gaps): (epoch - rollout) / updates
+                res["roofline"]["update_us"] = round(1e6 * (dt - t_roll) / (a.steps * n_upd_epoch), 1)
+            upd_per_epoch = OPT_EPOCHS * (wl["E"] * wl["T"] // wl["B"])
+            bucket = 4 * (int(ep.vf.hip.total_params) + 8)
+            if dist_on:
+                res["allreduce"] = LAST_ALLREDUCE
+                if world > 1:
+                    # prediction from THIS run's own compute time: strip the measured collectives, add the modelled ones
+                    ar_ms = (LAST_ALLREDUCE["us_per_call"] * 2 * upd_per_epoch * 1e-3) if LAST_ALLREDUCE else 0.0
+                    res["dp_model"] = dp_model(world, bucket, 12.0, None, max(1e3 * dt / a.steps - ar_ms, 1e-3), upd_per_epoch,
+                                               wl["E"] * wl["T"])
+                    res["dp_model"]["allreduce_us_measured"] = LAST_ALLREDUCE["us_per_call"] if LAST_ALLREDUCE else None
+            child = os.environ.get("V4L_BENCH_CHILD", "0") != "0"
+            if world == 1 and not a.no_parity and not child and a.workload in ("loco", "loco64"):
+                # side legs (driver-visible, all after the timed region): the other two compute modes with the same parity check, the DP
+                # schedule on one rank, the net's option variants (max_pool; token_norm, use_pytorch_encoder), and the multi-GPU cost model
+                notes = {"f32": "compute=f32: exact-fp32 MFMA (v_mfma_f32_16x16x4_f32) — the mode whose outputs meet the north star's "
+                                "1e-3 against the fp32 reference literally in every case (DESIGN.md section 2)",
+                         "f16": "compute=f16: IEEE half operands (v_mfma_f32_16x16x32_f16), fp32 accumulate, loss-gradient rows scaled by a "
+                                "power of two — bf16's speed, ~8 x closer to the fp32 reference (DESIGN.md section 2)",
+                         "bf16": "compute=bf16: bf16 operands (v_mfma_f32_16x16x32_bf16), fp32 accumulate"}
+                for other in ("f32", "f16", "bf16"):
+                    if other != a.compute:
+                        res[other + "_mode"] = dict(side_leg(a.workload, other, dev), parity_check=parity_check(wl, other, dev),
+                                                    note=notes[other])
+                        res[other + "_mode_value"] = res[other + "_mode"]["value"]  # flat: the driver's parser drops nested objects
+                    else:
+                        res[other + "_mode_value"] = value  # the headline's own mode, under the same flat name as the side legs
+                res["dp1_ingraph"] = dp1_ingraph_leg(a.workload, a.compute)
+                res["dp1_ingraph_value"] = res["dp1_ingraph"].get("value")
+                res["option_variant"] = side_leg("loco_max", a.compute, dev, steps=2, warmup=1)
+                # (round 5: the other two net options, fused since this round — DESIGN.md section 1)
+                res["option_variants"] = {w: side_leg(w, a.compute, dev, steps=2, warmup=1) for w in ("loco_tn", "loco_pe")}
+                alpha0 = (res["dp1_ingraph"].get("allreduce") or {}).get("us_per_call") or 12.0
+                res["dp_model"] = {str(n): dp_model(n, bucket, alpha0, None, 1e3 * dt / a.steps, upd_per_epoch, wl["E"] * wl["T"])
+                                   for n in (2, 4, 8)}
+            if world == 1 and not a.no_parity:
+                res["parity_check"] = parity_check(wl, a.compute, dev)
+                res["h2d_ms_per_step"] = round(h2d_per_step(wl, dev), 4)
+                res["h2d_note"] = ("pinned upload of E x (S+16384) fp32 observation rows per env step, NOT inside `value` (the "
+                                   "epoch is resident in HBM when the timed region starts); value_incl_h2d adds T x this, unoverlapped")
+                res["value_incl_h2d"] = round(frames * a.steps / (dt + a.steps * wl["T"] * res["h2d_ms_per_step"] * 1e-3), 1)
+                if not a.no_rollout and not a.no_reference_protocol:
+                    res["reference_protocol"] = reference_protocol(wl, a.compute, dev)
+                if not a.no_rollout and ep.actor is not None:
+                    # the headline WITH the critical-path transfers: the product's collector over a zero-cost env
+                    res["fast_collector"] = fast_collector(wl, a.compute, dev)
+                    res["value_incl_transfers"] = res["fast_collector"]["value"]
+                    res["value_incl_transfers_ratio"] = round(res["value_incl_transfers"] / value, 3)
+                    res["value_incl_transfers_note"] = (
+                        "`value` starts with the epoch resident in HBM (the contract); value_incl_transfers is the same epoch "
+                        "driven by VecOnPolicyCollector from float64 host rows: per env step a host cast, %d bytes read over PCIe by the kernels, "
+                        "2 launches and the action's D2H, serialised by the synchronous vec-env protocol"
+                        % res["fast_collector"]["h2d_bytes_per_env_step"])
+            if not a.no_cpu_baseline and world == 1:  # the host baseline is an N = 1 measurement (the other ranks would idle)
+                res["cpu_baseline"] = cpu_baseline(wl, a.compute)
+                res["vs_cpu_baseline"] = round(value / world / res["cpu_baseline"]["value"], 1)
+            if world == 1 and ep.actor is not None:
+                import vision4leg_amd.torchrl.policies as policies
+                res["batch1_inference"] = batch1_latency(ep, policies, dev)
+        elif dist_on:
+            ep.update()  # keep collectives matched with rank 0's profiled pass
     if dist_on:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

@@ -378,3 +378,22 @@ def test_bench_dump_outputs_names_dtypes_budget_and_fixed_sample(tmp_path):
     assert w.dtype == np.float32 and 0 < w.size < lin.weight.numel() and np.array_equal(w, load("c", "pf.weight"))
     assert np.isin(w, lin.weight.detach().numpy().reshape(-1)).all()
     assert np.array_equal(load("b", "rollout_actions"), ep.acts.numpy())
+
+
+def test_bench_full_is_opt_in(monkeypatch):
+    """A plain bench.py run measures the headline only; --full adds the legs with runs of their own. --breakdown is written by
+    the roofline's profiled step, so it asks for --full, and the 1-rank DP leg's child runs with --full (its all-reduce time
+    comes from the child's roofline pass)."""
+    import types
+    import bench
+    assert not bench.parse([]).full and bench.parse(["--full"]).full
+    with pytest.raises(SystemExit):
+        bench.parse(["--breakdown", "bd.txt"])
+    assert bench.parse(["--full", "--breakdown", "bd.txt"]).breakdown == "bd.txt"
+    seen = []
+    monkeypatch.setattr(bench.subprocess, "run",
+                        lambda cmd, **kw: seen.append(cmd) or types.SimpleNamespace(returncode=1, stdout="", stderr="stub"))
+    assert "error" in bench.dp1_ingraph_leg("loco", "f16")
+    cmd = seen[0]
+    child = bench.parse(cmd[cmd.index(os.path.join(bench.ROOT, "bench.py")) + 1:])
+    assert child.full and child.no_parity and child.no_cpu_baseline

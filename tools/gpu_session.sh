@@ -13,7 +13,7 @@ bench_ab() {  # tag, rounds, then pairs "name=libpath|env" ... : interleaved sho
     for spec in "$@"; do
       local name=${spec%%=*} rest=${spec#*=}
       ( for kv in ${rest//|/ }; do [ -n "$kv" ] && export "$kv"; done
-        python bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-parity --breakdown $O/${tag}_bd_${name}_$i.txt \
+        python bench.py --steps 12 --warmup 3 --full --no-cpu-baseline --no-parity --breakdown $O/${tag}_bd_${name}_$i.txt \
           > $O/${tag}_ab_${name}_$i.json 2> $O/${tag}_ab_${name}_$i.err )
     done
   done
@@ -45,7 +45,7 @@ pmc() {  # tag, script, counter groups... (one rocprofv3 run per group; summaris
 
 case $S in
 a)  # round 5, session A: today's baseline line, the rolled-layer-loop build (I-cache probe) A/B, I-fetch / wait counters, ckpt tests
-  python bench.py > $O/r5a_bench_base.json 2> $O/r5a_bench_base.err; tail -c 400 $O/r5a_bench_base.json
+  python bench.py --full > $O/r5a_bench_base.json 2> $O/r5a_bench_base.err; tail -c 400 $O/r5a_bench_base.json
   (timeout 600 python -m pytest tests/test_gpu_ckpt.py -q -m gpu --tb=short 2>&1 | tail -15) > $O/r5a_ckpt_tests.log; tail -5 $O/r5a_ckpt_tests.log
   bench_ab r5a 3 "base=" "roll=V4L_LIB=$REPO/vision4leg_amd/libv4l_hip_roll.so"
   G1="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_IFETCH SQ_IFETCH_LEVEL"
@@ -56,7 +56,7 @@ a)  # round 5, session A: today's baseline line, the rolled-layer-loop build (I-
   head -120 $O/r5a_base_pmc_summary.txt
   ;;
 b)  # round 5, session B: the extended default line (f32 / dp1 / option-variant legs), the rollout floor probe, scheduling variants
-  python bench.py > $O/r5b_bench_full.json 2> $O/r5b_bench_full.err; tail -c 3000 $O/r5b_bench_full.json; tail -5 $O/r5b_bench_full.err
+  python bench.py --full > $O/r5b_bench_full.json 2> $O/r5b_bench_full.err; tail -c 3000 $O/r5b_bench_full.json; tail -5 $O/r5b_bench_full.err
   [ -x tools/probe/rollout_floor ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/probe/rollout_floor.hip -o tools/probe/rollout_floor
   tools/probe/rollout_floor > $O/r5b_rollout_floor.txt 2>&1; cat $O/r5b_rollout_floor.txt
   L=$REPO/vision4leg_amd
@@ -68,7 +68,7 @@ c)  # round 5, session C: runtime knobs — where the kernel arguments live (dev
 full)  # the whole GPU suite + the default bench line (what the driver runs at round end)
   (timeout 1500 python -m pytest tests -q -m gpu --tb=short 2>&1 | tail -60) > $O/${TAG:-r6}_gpu_tests.log; tail -8 $O/${TAG:-r6}_gpu_tests.log
   cp $O/parity.json $O/${TAG:-r6}_parity.json 2>/dev/null
-  python bench.py > $O/${TAG:-r6}_bench_full.json 2> $O/${TAG:-r6}_bench_full.err; tail -c 600 $O/${TAG:-r6}_bench_full.json
+  python bench.py --full > $O/${TAG:-r6}_bench_full.json 2> $O/${TAG:-r6}_bench_full.err; tail -c 600 $O/${TAG:-r6}_bench_full.json
   ;;
 e)  # round 5, session E: the collector's hand-over variants (cast included) and fresh phase stamps of the rollout step kernels
   python tools/probe/collector_pipe.py > $O/r5e_collector_pipe.txt 2> $O/r5e_collector_pipe.err; cat $O/r5e_collector_pipe.txt
@@ -86,15 +86,15 @@ h)  # round 5, session H: launch-chain trims (update opening in registers, Adam 
   ;;
 evidence)  # the round's records for profiles/: tools/gpu_session.sh evidence <tag, e.g. r5>
   TAG=${1:-r5}; EV=$O/${TAG}_ev; mkdir -p $EV
-  python bench.py --steps 20 --warmup 5 --breakdown $EV/breakdown.txt > $EV/bench_full.json 2> $EV/bench_full.err
+  python bench.py --steps 20 --warmup 5 --full --breakdown $EV/breakdown.txt > $EV/bench_full.json 2> $EV/bench_full.err
   ( cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$EV/trace" -- \
-      python $REPO/bench.py --no-cpu-baseline --no-parity > "$EV/bench_traced.json" 2> "$EV/trace.log" )
+      python $REPO/bench.py --full --no-cpu-baseline --no-parity > "$EV/bench_traced.json" 2> "$EV/trace.log" )
   python tools/update_timeline.py $EV/trace $EV/update_timeline.txt > /dev/null
-  python tools/kernel_stats.py $EV/trace "rocprofv3 --kernel-trace of \`python bench.py --no-cpu-baseline --no-parity\` (1 warm-up + 3 timed epochs + 1 profiled rollout + update pass)" > $EV/kernel_stats.txt
+  python tools/kernel_stats.py $EV/trace "rocprofv3 --kernel-trace of \`python bench.py --full --no-cpu-baseline --no-parity\` (1 warm-up + 3 timed epochs + 1 profiled rollout + update pass)" > $EV/kernel_stats.txt
   tools/pmc_pass.sh "$EV/pmc" > "$EV/pmc.log" 2>&1
   python tools/pmc_traffic.py "$EV/pmc/summary.txt" "$EV/pmc_traffic.json" > /dev/null
   for w in cnn mlp loco64 loco_vis cnn_vis; do
-    python bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline --no-reference-protocol > $EV/bench_$w.json 2> $EV/bench_$w.err
+    python bench.py --workload $w --steps 10 --warmup 3 --full --no-cpu-baseline --no-reference-protocol > $EV/bench_$w.json 2> $EV/bench_$w.err
   done
   find "$EV" -name "*.csv" -size +1M -delete; find "$EV" -name "*.db" -delete
   du -sh $EV
