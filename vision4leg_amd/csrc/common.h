@@ -19,11 +19,11 @@ template <typename H, int N> struct HVec { typedef H type __attribute__((ext_vec
 void set_error(const char* fmt, ...);
 const char* last_error();
 
-#define V4L_HIP_CHECK(expr)                                                        \
+#define V4L_HIP_CHECK(...)  /* (variadic: template argument lists carry commas) */ \
   do {                                                                             \
-    hipError_t _e = (expr);                                                        \
+    hipError_t _e = (__VA_ARGS__);                                                 \
     if (_e != hipSuccess) {                                                        \
-      v4l::set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr,                 \
+      v4l::set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #__VA_ARGS__,          \
                      hipGetErrorString(_e));                                       \
       return -2;                                                                   \
     }                                                                              \

@@ -46,6 +46,13 @@ template <class F> static inline int by_half(int compute, F&& f) {
 static inline bool is_half(int compute) { return compute == V4L_BF16 || compute == V4L_F16; }
 // the 16-bit operand type a kernel family that only exists for 16-bit operands is instantiated with from a function templated on T
 template <typename T> struct HalfOf { typedef typename std::conditional<sizeof(T) == 2, T, __bf16>::type type; };
+// The dynamic-LDS limit of kernel instance K, raised to `bytes` once per process (a function-local static: its initialisation is
+// thread-safe). Every call returns the stored result, so a failure is reported through V4L_HIP_CHECK on every launch path.
+template <auto K> static hipError_t lds_limit(size_t bytes) {
+  static const hipError_t e =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  return e;
+}
 static int sw_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static const bool g_trace = sw_on("V4L_TRACE");
 #define V4L_TRACE(...) do { if (v4l::g_trace) { fprintf(stderr, "[v4l] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
@@ -273,12 +280,7 @@ static int wgrad_finish(Ctx& c) {
 static int fb_finish(Ctx& c, hipStream_t s) {
   if (!c.fb_pending) return 0;
   c.fb_pending = false;
-  static bool attr = false;
-  if (!attr) {
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fb_loss_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)FbFinishLds::bytes));
-    attr = true;
-  }
+  V4L_HIP_CHECK(lds_limit<&fb_loss_finish_kernel>(FbFinishLds::bytes));
   g_op = "loss";
   V4L_KLAUNCH("fb_loss_finish", 0, s, fb_loss_finish_kernel, dim3(1), dim3(256), FbFinishLds::bytes, s, c.fb_args, c.fb_blocks, c.fb_n);
   V4L_LAUNCH_CHECK();
@@ -331,14 +333,8 @@ static int wgrad_dense(Ctx& c, hipStream_t ds, hipStream_t dg) {
     }
   }
   constexpr size_t dense_lds = TnWideLds<T>::max_bytes > TnBodyLds<T, 64, 1>::bytes ? TnWideLds<T>::max_bytes : TnBodyLds<T, 64, 1>::bytes;
-  static bool attr_done = false;
-  if (!attr_done) {
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_wide_kernel<T>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)TnWideLds<T>::max_bytes));
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_dense_kernel<T>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)dense_lds));
-    attr_done = true;
-  }
+  V4L_HIP_CHECK(lds_limit<&gemm_tn_wide_kernel<T>>(TnWideLds<T>::max_bytes));
+  V4L_HIP_CHECK(lds_limit<&gemm_tn_dense_kernel<T>>(dense_lds));
   if (gb > 0 && wb > 0) {
     g_op = "layer.wgrad";  // (the layers' share dominates: 8 of the ~20 problems, 2/3 of the blocks)
     V4L_KLAUNCH("gemm_tn_dense", net->wide_flops + net->tnp_flops, dg, gemm_tn_dense_kernel<T>, dim3((unsigned)(wb + gb)), dim3(256),
@@ -619,15 +615,8 @@ template <typename T>
 static int conv_stack_bwd_fused(Ctx& c, const T* image, const int* rowidx, int n, const float* c1, const float* c2,
                                 const float* dc3, float* dc2_tap, float* dc1_tap) {
   v4l_net* N = c.net;
-  static bool attr_done = false;
-  if (!attr_done) {
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_conv_kernel<T>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)BwdConvLds<T>::bytes));
-    if constexpr (sizeof(T) == 2)
-      V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_conv_kernel<T, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)BwdConvLds<T>::bytes));
-    attr_done = true;
-  }
+  V4L_HIP_CHECK(lds_limit<&bwd_conv_kernel<T>>(BwdConvLds<T>::bytes));
+  if constexpr (sizeof(T) == 2) V4L_HIP_CHECK(lds_limit<&bwd_conv_kernel<T, true>>(BwdConvLds<T>::bytes));
   // c1 / c2 in T: what the training encoder of THIS workspace's last forward wrote (the mark is the workspace's c1 address, so a
   // forward of the same net over another workspace in between — HipNet.value() at another batch size — does not change it)
   const bool a16 = sizeof(T) == 2 && N->acts16_c1 != nullptr && N->acts16_c1 == c1;
@@ -1294,12 +1283,7 @@ int v4l_net::forward_t(const float* state, const T* image, const int* rowidx, in
   auto train_enc = [&](auto mode_tag, float* x0, float* s_h2, int ld_h2, bool proprio = true) -> int {
     constexpr int MODE = decltype(mode_tag)::value;
     typedef typename HalfOf<T>::type H;  // (train_enc_ok: 16-bit operand types only)
-    static bool attr = false;
-    if (!attr) {
-      V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&train_encoder_kernel<H, MODE>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)TrainEncLds::bytes));
-      attr = true;
-    }
+    V4L_HIP_CHECK(lds_limit<&train_encoder_kernel<H, MODE>>(TrainEncLds::bytes));
     const H* pb = (const H*)packed;
     const bool tok = MODE == ENC_TOK17 || MODE == ENC_TOK16, prop = proprio && (MODE == ENC_TOK17 || MODE == ENC_FUSE);
     InfEncFrag ef;
@@ -1379,12 +1363,7 @@ int v4l_net::forward_t(const float* state, const T* image, const int* rowidx, in
     if (enc_ws == nullptr && stage != 2 && fused_enc) {
       // one launch for the whole encoder (csrc/infer.h): a block per sample runs conv1..3 + up-conv out of LDS, extra
       // blocks run the proprio MLP; the activations backward_t needs are saved on the way
-      static bool attr_done = false;
-      if (!attr_done) {
-        V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&infer_encoder_kernel<T>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)InfEncLds<T>::bytes));
-        attr_done = true;
-      }
+      V4L_HIP_CHECK(lds_limit<&infer_encoder_kernel<T>>(InfEncLds<T>::bytes));
       const T* pk = (const T*)packed;
       InfEnc en;
       en.w1 = pk + conv[0].pk; en.w2 = pk + conv[1].pk; en.w3 = pk + conv[2].pk; en.wup = pk + upconv.pk;
@@ -1470,24 +1449,13 @@ int v4l_net::forward_t(const float* state, const T* image, const int* rowidx, in
     bool wps_layers_done = false;  // (use_pytorch_encoder on the wave-per-sample layers: norm, pooling and heads still to come)
     if ((stacked && wps_layers() && wps_bwd_plain()) || vis_wps || opt_wps) {
       // wave-per-sample launch (csrc/wps.h): both layers + the pooled heads, 4 samples per block, weights resident in LDS
-      static bool wps_attr = false;
-      if (!wps_attr) {
-        V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wps_layer_fwd_kernel<T, true, 2, false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)WpsFwdLds<T>::bytes));
-        V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wps_layer_fwd_kernel<T, true, 2, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)WpsFwdLds<T>::bytes));
-        V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wps_layer_fwd_kernel<T, true, 2, false, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)WpsFwdLds<T>::bytes));
-        V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wps_layer_fwd_kernel<T, true, 2, true, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)WpsFwdLds<T>::bytes));
-        V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wps_layer_fwd_kernel<T, true, 2, false, 2>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)WpsFwdLds<T>::bytes));
-        V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wps_layer_fwd_kernel<T, false, 2, false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)WpsFwdLds<T>::bytes));
-        V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wps_layer_fwd_kernel<T, false, 2, false, 2>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)WpsFwdLds<T>::bytes));
-        wps_attr = true;
-      }
+      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, true, 2, false>>(WpsFwdLds<T>::bytes));
+      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, true, 2, true>>(WpsFwdLds<T>::bytes));
+      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, true, 2, false, true>>(WpsFwdLds<T>::bytes));
+      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, true, 2, true, true>>(WpsFwdLds<T>::bytes));
+      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, true, 2, false, 2>>(WpsFwdLds<T>::bytes));
+      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, false, 2, false>>(WpsFwdLds<T>::bytes));
+      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, false, 2, false, 2>>(WpsFwdLds<T>::bytes));
       const bool taps = sw_on("V4L_LAYER_TAPS");  // (read per call: tests switch it)
       const T* base = (const T*)packed;
       InfLayerStack stk;
@@ -1549,22 +1517,16 @@ int v4l_net::forward_t(const float* state, const T* image, const int* rowidx, in
       wps_layers_done = true;
     }
     for (int l = 0; l < c.n_layers && fused_layers; l += stacked ? 2 : 1) {
-      static bool attr_done = false;
       static int spw = 2;  // samples per block: 2 (48 MFMA rows, 2 blocks/CU: measured 20 % faster) or 4 (80 rows, 1 block/CU)
-      if (!attr_done) {
-        spw = 2;
-        constexpr bool spw4_fits = InfLayLds<T, 4>::bytes <= 160 * 1024;  // (not in the fp32 parity mode: 168 KB)
-        auto lds = [](const void* fn, size_t bytes) { return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
-        if (spw4_fits) {
-          V4L_HIP_CHECK(lds(reinterpret_cast<const void*>(&infer_layer_kernel<T, 4, false, 1>), InfLayLds<T, 4>::bytes));
-          V4L_HIP_CHECK(lds(reinterpret_cast<const void*>(&infer_layer_kernel<T, 4, true, 1>), InfLayLds<T, 4>::bytes));
-          V4L_HIP_CHECK(lds(reinterpret_cast<const void*>(&infer_layer_kernel<T, 4, true, 2>), InfLayLds<T, 4>::bytes));
-        }
-        V4L_HIP_CHECK(lds(reinterpret_cast<const void*>(&infer_layer_kernel<T, 2, false, 1>), InfLayLds<T, 2>::bytes));
-        V4L_HIP_CHECK(lds(reinterpret_cast<const void*>(&infer_layer_kernel<T, 2, true, 1>), InfLayLds<T, 2>::bytes));
-        V4L_HIP_CHECK(lds(reinterpret_cast<const void*>(&infer_layer_kernel<T, 2, true, 2>), InfLayLds<T, 2>::bytes));
-        attr_done = true;
+      constexpr bool spw4_fits = InfLayLds<T, 4>::bytes <= 160 * 1024;  // (not in the fp32 parity mode: 168 KB)
+      if (spw4_fits) {
+        V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, 4, false, 1>>(InfLayLds<T, 4>::bytes));
+        V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, 4, true, 1>>(InfLayLds<T, 4>::bytes));
+        V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, 4, true, 2>>(InfLayLds<T, 4>::bytes));
       }
+      V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, 2, false, 1>>(InfLayLds<T, 2>::bytes));
+      V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, 2, true, 1>>(InfLayLds<T, 2>::bytes));
+      V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, 2, true, 2>>(InfLayLds<T, 2>::bytes));
       const T* base = (const T*)packed;
       InfLayerStack stk;
       memset(&stk, 0, sizeof(stk));
@@ -1671,14 +1633,8 @@ int v4l_net::forward_t(const float* state, const T* image, const int* rowidx, in
     a.b0 = p[head[0].b]; a.b1 = p[head[1].b]; a.b2 = p[head[2].b];
     a.h0 = ws + L.hh[0]; a.h1 = ws + L.hh[1]; a.out = ws + L.out;
     a.n = n; a.nout = c.out_dim;
-    static bool attr_done = false;
-    if (!attr_done) {
-      V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_stack_fwd_kernel<T, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)DsFwdLds<T>::bytes));
-      V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_stack_fwd_kernel<T, false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)DsFwdLds<T>::bytes));
-      attr_done = true;
-    }
+    V4L_HIP_CHECK(lds_limit<&dense_stack_fwd_kernel<T, true>>(DsFwdLds<T>::bytes));
+    V4L_HIP_CHECK(lds_limit<&dense_stack_fwd_kernel<T, false>>(DsFwdLds<T>::bytes));
     g_op = "dense.stack";
     const double fl = 2.0 * n * ((fuse ? 1024.0 * 256 + 512.0 * 256 : 1024.0 * 256) + 256.0 * 256 + 256.0 * c.out_dim);
     const dim3 grid(cdiv(n, 16 * DsCfg<T>::MT));
@@ -1816,14 +1772,8 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
       a.cat = ws + L.vis; a.e0 = ws + L.eh[0]; a.dcat = hand; a.de0 = dehp[0];
     }
     a.n = n;
-    static bool attr_done = false;
-    if (!attr_done) {
-      V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_stack_bwd_kernel<T, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)DsBwdLds<T>::bytes));
-      V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_stack_bwd_kernel<T, false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)DsBwdLds<T>::bytes));
-      attr_done = true;
-    }
+    V4L_HIP_CHECK(lds_limit<&dense_stack_bwd_kernel<T, true>>(DsBwdLds<T>::bytes));
+    V4L_HIP_CHECK(lds_limit<&dense_stack_bwd_kernel<T, false>>(DsBwdLds<T>::bytes));
     g_op = "dense.stack.bwd";
     const double fl = 2.0 * n * (256.0 * c.out_dim + 256.0 * 256 + (fuse ? 512.0 * 256 + 1024.0 * 256 + 256.0 * 256 : 1024.0 * 256));
     const dim3 grid(cdiv(n, 16 * DsCfg<T>::MT));
@@ -1992,12 +1942,7 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
     const double fl = 2 * 4.0 * n * 872576.0 + (head_ext ? 0.0 : 2 * fl_heads) + (tok0_ext ? 0.0 : fl_tok0) + 2.0 * n * 16 * 64 * 64;
 #define V4L_WPS_BWD(TAPS_, VIS_, HIN_, TIN_, MODE_)                                                                       \
   do {                                                                                                                    \
-    static bool attr_ = false;                                                                                            \
-    if (!attr_) {                                                                                                         \
-      V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wps_layer_bwd_kernel<T, 2, TAPS_, VIS_, HIN_, TIN_, MODE_>), \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)WpsBwdLds<T>::bytes));          \
-      attr_ = true;                                                                                                       \
-    }                                                                                                                     \
+    V4L_HIP_CHECK(lds_limit<&wps_layer_bwd_kernel<T, 2, TAPS_, VIS_, HIN_, TIN_, MODE_>>(WpsBwdLds<T>::bytes));            \
     V4L_KLAUNCH("wps_layer_bwd_stack", fl, s, (wps_layer_bwd_kernel<T, 2, TAPS_, VIS_, HIN_, TIN_, MODE_>), dim3(nblk), dim3(256), \
                 (WpsBwdLds<T>::bytes), s, d, bh, bt, tx, n);                                                              \
   } while (0)
@@ -2034,14 +1979,8 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
       cx.slab_used += 2 * (int64_t)nblk * FB_PART;
       V4L_REQUIRE(cx.slab_used <= slab_cap, "internal: weight-grad slab arena overflow");
       const double fl_fb = fl + 2.0 * n * (2 * 872576.0 + 99840.0);  // + the two layer forwards and the heads' forward
-      static bool attr_fb = false;
-      if (!attr_fb) {
-        V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wps_layer_fb_kernel<T, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)WpsFbLds<T>::bytes));
-        V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wps_layer_fb_kernel<T, false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)WpsFbLds<T>::bytes));
-        attr_fb = true;
-      }
+      V4L_HIP_CHECK(lds_limit<&wps_layer_fb_kernel<T, true>>(WpsFbLds<T>::bytes));
+      V4L_HIP_CHECK(lds_limit<&wps_layer_fb_kernel<T, false>>(WpsFbLds<T>::bytes));
       if (tok0_ext)
         V4L_KLAUNCH("wps_layer_fb_stack", fl_fb, s, (wps_layer_fb_kernel<T, false>), dim3(nblk), dim3(256), (WpsFbLds<T>::bytes), s, fst,
                     fhd, d, bh, bt, tx, lo, n);
@@ -2104,25 +2043,17 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
     cx.wps_used = true;
   }
   for (int l = c.n_layers - 1; l >= 0 && fused_bwd && !wps; l -= stacked ? 2 : 1) {
-    static bool attr_done = false;
     static int spw = 4;  // samples per block: 4 (80 MFMA rows, 1 block per CU) or 2 (48 rows, 2 blocks per CU): measured equal
-    if (!attr_done) {
-      const void* f4[5] = {reinterpret_cast<const void*>(&bwd_layer_kernel<T, 4, false, false, 1>),
-                           reinterpret_cast<const void*>(&bwd_layer_kernel<T, 4, true, false, 1>),
-                           reinterpret_cast<const void*>(&bwd_layer_kernel<T, 4, false, true, 1>),
-                           reinterpret_cast<const void*>(&bwd_layer_kernel<T, 4, true, true, 1>),
-                           reinterpret_cast<const void*>(&bwd_layer_kernel<T, 4, true, true, 2>)};
-      const void* f2[5] = {reinterpret_cast<const void*>(&bwd_layer_kernel<T, 2, false, false, 1>),
-                           reinterpret_cast<const void*>(&bwd_layer_kernel<T, 2, true, false, 1>),
-                           reinterpret_cast<const void*>(&bwd_layer_kernel<T, 2, false, true, 1>),
-                           reinterpret_cast<const void*>(&bwd_layer_kernel<T, 2, true, true, 1>),
-                           reinterpret_cast<const void*>(&bwd_layer_kernel<T, 2, true, true, 2>)};
-      for (const void* fn : f4)
-        V4L_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BwdLayLds<T, 4>::bytes));
-      for (const void* fn : f2)
-        V4L_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BwdLayLds<T, 2>::bytes));
-      attr_done = true;
-    }
+    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 4, false, false, 1>>(BwdLayLds<T, 4>::bytes));
+    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 4, true, false, 1>>(BwdLayLds<T, 4>::bytes));
+    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 4, false, true, 1>>(BwdLayLds<T, 4>::bytes));
+    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 4, true, true, 1>>(BwdLayLds<T, 4>::bytes));
+    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 4, true, true, 2>>(BwdLayLds<T, 4>::bytes));
+    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 2, false, false, 1>>(BwdLayLds<T, 2>::bytes));
+    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 2, true, false, 1>>(BwdLayLds<T, 2>::bytes));
+    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 2, false, true, 1>>(BwdLayLds<T, 2>::bytes));
+    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 2, true, true, 1>>(BwdLayLds<T, 2>::bytes));
+    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 2, true, true, 2>>(BwdLayLds<T, 2>::bytes));
     const int nblk = cdiv(n, spw);
     const int nl = stacked ? 2 : 1;
     const T* base = (const T*)packed;
@@ -2297,43 +2228,88 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
 static inline long long actor_t_plus1(const v4l_actor* a, hipStream_t s) {
   return (a->t_host >= 0 && !capturing(s)) ? a->t_host + 1 : 0;
 }
-// Fused rollout step for the shipped LocoTransformer shape (csrc/infer.h): 4 launches instead of ~50.
-static bool actor_fusable(const v4l_actor* a) {
-  const v4l_net_cfg &p = a->pf->cfg, &v = a->vf->cfg;
-  auto ok = [](const v4l_net_cfg& c) {
-    const bool trunk = c.n_head_hidden == 2 && c.head_hidden[0] == 256 && c.head_hidden[1] == 256 && c.ff_dim == 256;
+// The buffers of one rollout step (v4l_actor_step's arguments). img16 / ld_img16: v4l_actor_step_split's bf16 depth stacks
+// [E][ld_img16] (null: the image is part of the fp32 observation rows).
+struct StepIO {
+  const float *obs, *eps;
+  float* state_roll;
+  void* image_roll;
+  float *acts_roll, *values_roll, *logp_roll, *action, *mean, *stdv, *ent, *value;
+  const void* img16;
+  int64_t ld_img16;
+};
+// the epilogue of a fused step: sample the action, file action / value / log-prob, write the step's outputs
+static InfFinish step_finish(const v4l_actor* a, const StepIO& io, hipStream_t s) {
+  const v4l_net* pf = a->pf;
+  InfFinish fin;
+  memset(&fin, 0, sizeof(fin));
+  fin.ctl = a->ctl; fin.logstd = pf->p[pf->logstd]; fin.eps = io.eps; fin.A = pf->cfg.out_dim; fin.tanh_action = pf->cfg.tanh_action;
+  fin.t_plus1 = actor_t_plus1(a, s);
+  fin.acts_roll = io.acts_roll; fin.values_roll = io.values_roll; fin.logp_roll = io.logp_roll; fin.action = io.action;
+  fin.mean = io.mean; fin.stdv = io.stdv; fin.ent = io.ent; fin.value = io.value;
+  return fin;
+}
+
+// The kernels that run an actor's step, in the order step_route tries them
+enum class StepRoute {
+  MLP_ONE_BLOCK,   // state MLP, 16-bit: rollout_mlp2_kernel, one block per net for all E rows
+  MLP_PER_SAMPLE,  // state MLP: rollout_mlp_kernel
+  CNN_DENSE,       // NatureCNN, 16-bit: rollout_encoder2_kernel + rollout_dense_kernel (csrc/rollout_dense.h)
+  CNN_PER_SAMPLE,  // NatureCNN: rollout_cnn_kernel
+  STACK_TOK16,     // vision-only LocoTransformer, 16-bit: rollout_encoder2_kernel<ENC_TOK16> + rollout_stack_kernel
+  STACK_TOK17,     // LocoTransformer, 16-bit: rollout_encoder2_kernel<ENC_TOK17> + rollout_stack_kernel
+  STACK_F32ENC,    // LocoTransformer, fp32: rollout_encoder_kernel + rollout_stack_kernel
+  GENERAL,         // layer by layer (forward_t of each net) + act_finish_kernel
+};
+// the shapes the fused kernels are specialised for: the proprio MLP 256-256 on at most 128 inputs, heads 256-256, 4 x 64 x 64 depth
+static bool mlp_256(const v4l_net_cfg& c) {
+  return c.n_enc_hidden == 2 && c.enc_hidden[0] == 256 && c.enc_hidden[1] == 256 && c.state_dim <= 128;
+}
+static bool head_256(const v4l_net_cfg& c) { return c.n_head_hidden == 2 && c.head_hidden[0] == 256 && c.head_hidden[1] == 256; }
+static bool depth_64(const v4l_net_cfg& c) { return c.in_channels == 4 && c.img_hw == 64; }
+static StepRoute step_route(const v4l_actor* a, int shared_encoder) {
+  const v4l_net *pf = a->pf, *vf = a->vf;
+  const v4l_net_cfg &p = pf->cfg, &v = vf->cfg;
+  if (!shared_encoder) return StepRoute::GENERAL;
+  auto both = [&](auto ok) { return ok(p) && ok(v); };
+  auto frag_heads = [&] { return pf->head[0].pkf >= 0 && vf->head[0].pkf >= 0; };  // fragment-order packs of the heads
+  // tanh_action policies (TanhNormal): the fused kernels' epilogues sample through tanh like act_finish_kernel (round 5), except
+  // the one-block state-MLP and the dense NatureCNN kernels (rollout_dense.h) — such a policy takes the next family
+  const bool tanh_pol = p.tanh_action != 0;
+  if (both([](const v4l_net_cfg& c) { return c.kind == V4L_NET_MLP && mlp_256(c) && head_256(c); }) && pf->enc[0].Kp <= 128) {
+    const bool one_block = is_half(p.compute) && a->E <= 64 && p.out_dim <= 16 && pf->enc[0].Kp == 128 && pf->enc[0].pkf >= 0 &&
+                           frag_heads();
+    return one_block && !tanh_pol ? StepRoute::MLP_ONE_BLOCK : StepRoute::MLP_PER_SAMPLE;
+  }
+  const bool dense_cnn = both([](const v4l_net_cfg& c) {
+    if (!(head_256(c) && depth_64(c) && c.out_dim <= 16 && is_half(c.compute))) return false;
+    return c.kind == V4L_NET_CNN_VIS || (c.kind == V4L_NET_CNN && mlp_256(c) && c.visual_dim == 256);
+  }) && a->E <= 64 && pf->conv[0].pkf >= 0 && frag_heads() && (p.kind == V4L_NET_CNN_VIS || pf->enc[0].Kp == 128);
+  if (dense_cnn && !tanh_pol) return StepRoute::CNN_DENSE;
+  if (both([](const v4l_net_cfg& c) {
+        return c.kind == V4L_NET_CNN && mlp_256(c) && head_256(c) && c.visual_dim == 256 && depth_64(c);
+      }) && pf->enc[0].Kp <= 128)
+    return StepRoute::CNN_PER_SAMPLE;
+  // LocoTransformer, two layers (max_pool: a flag of rollout_stack_kernel's pooling — the stack itself is the same; token_norm /
+  // use_pytorch_encoder: the same kernel with the extra norm in front of / behind the layers, one of the two, set alike on both nets)
+  const bool stack = both([](const v4l_net_cfg& c) {
+    const bool trunk = head_256(c) && c.ff_dim == 256 && c.n_layers == 2;
     if (c.kind == V4L_NET_LOCO_VIS) return trunk && is_half(c.compute);  // (16 tokens: 16-bit kernels only)
-    return c.kind == V4L_NET_LOCO && c.n_enc_hidden == 2 && c.enc_hidden[0] == 256 && c.enc_hidden[1] == 256 && trunk &&
-           c.state_dim <= 128;
-  };
-  // (max_pool: a flag of rollout_stack_kernel's pooling — the stack itself is the same)
-  const bool opt_ok = p.token_norm == v.token_norm && p.pytorch_encoder == v.pytorch_encoder && !(p.token_norm && p.pytorch_encoder);
-  return ok(p) && ok(v) && opt_ok && p.n_layers == 2 && v.n_layers == 2 && a->E <= 64 && a->pf->head.size() == 3 &&
-         a->pf->head[0].pkf >= 0 && a->vf->head[0].pkf >= 0;
+    return c.kind == V4L_NET_LOCO && mlp_256(c) && trunk;
+  }) && p.token_norm == v.token_norm && p.pytorch_encoder == v.pytorch_encoder && !(p.token_norm && p.pytorch_encoder) &&
+                     a->E <= 64 && pf->head.size() == 3 && frag_heads();
+  if (!stack) return StepRoute::GENERAL;
+  if (p.kind == V4L_NET_LOCO_VIS) return StepRoute::STACK_TOK16;
+  if (is_half(p.compute) && pf->enc.size() == 2 && pf->enc[0].Kp == 128 && pf->conv[0].pkf >= 0) return StepRoute::STACK_TOK17;
+  return StepRoute::STACK_F32ENC;  // (fp32 parity mode: fragments twice the size, weights streamed per wave)
 }
 
 // NatureCNN fuse nets of the shipped shape: one launch per env step (rollout_cnn_kernel)
-static bool actor_fusable_cnn(const v4l_actor* a) {
-  const v4l_net_cfg &p = a->pf->cfg, &v = a->vf->cfg;
-  auto ok = [](const v4l_net_cfg& c) {
-    return c.kind == V4L_NET_CNN && c.n_enc_hidden == 2 && c.enc_hidden[0] == 256 && c.enc_hidden[1] == 256 &&
-           c.n_head_hidden == 2 && c.head_hidden[0] == 256 && c.head_hidden[1] == 256 && c.visual_dim == 256 &&
-           c.state_dim <= 128 && c.in_channels == 4 && c.img_hw == 64;
-  };
-  return ok(p) && ok(v);
-}
 template <typename T>
-static int run_actor_fused_cnn(v4l_actor* a, const float* obs, const float* eps, float* state_roll, void* image_roll,
-                               float* acts_roll, float* values_roll, float* logp_roll, float* action, float* mean, float* stdv,
-                               float* ent, float* value, hipStream_t s) {
+static int run_actor_fused_cnn(v4l_actor* a, const StepIO& io, hipStream_t s) {
   v4l_net *pf = a->pf, *vf = a->vf;
   const int E = a->E;
-  static bool attr_done = false;
-  if (!attr_done) {
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_cnn_kernel<T>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)RollCnnLds<T>::bytes));
-    attr_done = true;
-  }
+  V4L_HIP_CHECK(lds_limit<&rollout_cnn_kernel<T>>(RollCnnLds<T>::bytes));
   const T* pk = (const T*)pf->packed;
   const T* vk = (const T*)vf->packed;
   const Layout Lp = pf->layout(E), Lv = vf->layout(E);
@@ -2354,77 +2330,42 @@ static int run_actor_fused_cnn(v4l_actor* a, const float* obs, const float* eps,
   };
   head(hd.n[0], pf, pk, ws_pf + Lp.out);
   head(hd.n[1], vf, vk, ws_vf + Lv.out);
-  InfFinish fin;
-  memset(&fin, 0, sizeof(fin));
-  fin.ctl = a->ctl; fin.logstd = pf->p[pf->logstd]; fin.eps = eps; fin.A = pf->cfg.out_dim; fin.tanh_action = pf->cfg.tanh_action;
-  fin.t_plus1 = actor_t_plus1(a, s);
-  fin.acts_roll = acts_roll; fin.values_roll = values_roll; fin.logp_roll = logp_roll; fin.action = action;
-  fin.mean = mean; fin.stdv = stdv; fin.ent = ent; fin.value = value;
+  const InfFinish fin = step_finish(a, io, s);
   g_op = "step";
   V4L_KLAUNCH("rollout_cnn", 2.0 * 2 * E * (3612672.0 + 1024 * 256 + 2 * 128 * 256 + 512 * 256 + 2 * 256 * 256), s, rollout_cnn_kernel<T>,
-              dim3(E, 2), dim3(1024), RollCnnLds<T>::bytes, s, (const ActCtl*)a->ctl, obs, E, en, hd, fin, state_roll,
-              (T*)image_roll);
+              dim3(E, 2), dim3(1024), RollCnnLds<T>::bytes, s, (const ActCtl*)a->ctl, io.obs, E, en, hd, fin, io.state_roll,
+              (T*)io.image_roll);
   V4L_LAUNCH_CHECK();
   return 0;
 }
 
-// NatureCNN nets (fuse net and vision-only), bf16: the step as batched GEMMs over all E rows (csrc/rollout_dense.h)
-static bool actor_dense_cnn(const v4l_actor* a) {
-  const v4l_net_cfg &p = a->pf->cfg, &v = a->vf->cfg;
-  auto ok = [](const v4l_net_cfg& c) {
-    const bool shape = c.n_head_hidden == 2 && c.head_hidden[0] == 256 && c.head_hidden[1] == 256 && c.in_channels == 4 &&
-                       c.img_hw == 64 && c.out_dim <= 16 && is_half(c.compute);
-    if (c.kind == V4L_NET_CNN)
-      return shape && c.n_enc_hidden == 2 && c.enc_hidden[0] == 256 && c.enc_hidden[1] == 256 && c.visual_dim == 256 &&
-             c.state_dim <= 128;
-    return shape && c.kind == V4L_NET_CNN_VIS;
-  };
-  return ok(p) && ok(v) && a->E <= 64 && a->pf->conv[0].pkf >= 0 && a->pf->head[0].pkf >= 0 && a->vf->head[0].pkf >= 0 &&
-         (p.kind == V4L_NET_CNN_VIS || a->pf->enc[0].Kp == 128);
-}
 // rollout_encoder2_kernel<MODE> on the step's observation: fp32 rows [E][S + C*H*W], or — v4l_actor_step_split — fp32 proprio
-// rows [E][S] + bf16 depth stacks (a->img16)
+// rows [E][S] + bf16 depth stacks (io.img16)
 template <typename H, int MODE, bool IMG16>
-static int launch_encoder2_t(v4l_actor* a, hipStream_t s, double flops, dim3 grid, const float* obs, int E, const InfEncFrag& ef,
-                             float* state_roll, H* image_roll, float* x0, H* featv, H* featp) {
-  static bool attr = false;
-  if (!attr) {
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_encoder2_kernel<H, MODE, IMG16>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)RollEnc2Lds::bytes));
-    attr = true;
-  }
+static int launch_encoder2_t(v4l_actor* a, const StepIO& io, hipStream_t s, double flops, dim3 grid, const InfEncFrag& ef, float* x0,
+                             H* featv, H* featp) {
+  V4L_HIP_CHECK(lds_limit<&rollout_encoder2_kernel<H, MODE, IMG16>>(RollEnc2Lds::bytes));
   const int img_elems = a->pf->cfg.in_channels * a->pf->cfg.img_hw * a->pf->cfg.img_hw;
   const int ld_obs = IMG16 ? ef.S : ef.S + img_elems;
   V4L_KLAUNCH("rollout_encoder", flops, s, (rollout_encoder2_kernel<H, MODE, IMG16>), grid, dim3(1024), RollEnc2Lds::bytes, s,
-              (const ActCtl*)a->ctl, obs, ld_obs, (const H*)a->img16, a->ld_img16, E, ef, state_roll, image_roll, x0, featv,
-              featp, actor_t_plus1(a, s));
+              (const ActCtl*)a->ctl, io.obs, ld_obs, (const H*)io.img16, io.ld_img16, a->E, ef, io.state_roll, (H*)io.image_roll, x0,
+              featv, featp, actor_t_plus1(a, s));
   V4L_LAUNCH_CHECK();
   return 0;
 }
 template <typename H, int MODE>
-static int launch_encoder2(v4l_actor* a, hipStream_t s, double flops, dim3 grid, const float* obs, int E, const InfEncFrag& ef,
-                           float* state_roll, H* image_roll, float* x0, H* featv, H* featp) {
-  return a->img16 ? launch_encoder2_t<H, MODE, true>(a, s, flops, grid, obs, E, ef, state_roll, image_roll, x0, featv, featp)
-                  : launch_encoder2_t<H, MODE, false>(a, s, flops, grid, obs, E, ef, state_roll, image_roll, x0, featv, featp);
+static int launch_encoder2(v4l_actor* a, const StepIO& io, hipStream_t s, double flops, dim3 grid, const InfEncFrag& ef, float* x0,
+                           H* featv, H* featp) {
+  return io.img16 ? launch_encoder2_t<H, MODE, true>(a, io, s, flops, grid, ef, x0, featv, featp)
+                  : launch_encoder2_t<H, MODE, false>(a, io, s, flops, grid, ef, x0, featv, featp);
 }
 
+// NatureCNN nets (fuse net and vision-only), bf16: the step as batched GEMMs over all E rows (csrc/rollout_dense.h)
 template <typename H>
-static int run_actor_dense_cnn(v4l_actor* a, const float* obs, const float* eps, float* state_roll, void* image_roll,
-                               float* acts_roll, float* values_roll, float* logp_roll, float* action, float* mean, float* stdv,
-                               float* ent, float* value, hipStream_t s) {
+static int run_actor_dense_cnn(v4l_actor* a, const StepIO& io, hipStream_t s) {
   v4l_net *pf = a->pf, *vf = a->vf;
   const int E = a->E;
   const bool fuse = pf->cfg.kind == V4L_NET_CNN;
-  static bool attr_done = false;
-  if (!attr_done) {
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_encoder2_kernel<H, ENC_FUSE>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)RollEnc2Lds::bytes));
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_encoder2_kernel<H, ENC_FLAT>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)RollEnc2Lds::bytes));
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_head_kernel<H>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)RollHeadLds::bytes));
-    attr_done = true;
-  }
   const H* pk = (const H*)pf->packed;
   const H* vk = (const H*)vf->packed;
   const Layout Lp = pf->layout(E), Lv = vf->layout(E);
@@ -2450,20 +2391,14 @@ static int run_actor_dense_cnn(v4l_actor* a, const float* obs, const float* eps,
   if (fuse) {
     ef.wf1 = pk + pf->enc[0].pkf; ef.wf2 = pk + pf->enc[1].pkf; ef.wpr = ef.wf2;
     ef.bf1 = pf->p[pf->enc[0].b]; ef.bf2 = pf->p[pf->enc[1].b]; ef.bpr = ef.bf2;
-    if (int rc = launch_encoder2<H, ENC_FUSE>(a, s, 2.0 * E * (3612672.0 + 128 * 256 + 256 * 256), dim3(E + cdiv(E, 32)), obs, E, ef,
-                                           state_roll, (H*)image_roll, (float*)nullptr, featv, cat))
+    if (int rc = launch_encoder2<H, ENC_FUSE>(a, io, s, 2.0 * E * (3612672.0 + 128 * 256 + 256 * 256), dim3(E + cdiv(E, 32)), ef,
+                                           (float*)nullptr, featv, cat))
       return rc;
   } else {
-    if (int rc = launch_encoder2<H, ENC_FLAT>(a, s, 2.0 * E * 3612672.0, dim3(E), obs, E, ef, state_roll, (H*)image_roll,
-                                           (float*)nullptr, featv, (H*)nullptr))
+    if (int rc = launch_encoder2<H, ENC_FLAT>(a, io, s, 2.0 * E * 3612672.0, dim3(E), ef, (float*)nullptr, featv, (H*)nullptr))
       return rc;
   }
-  InfFinish fin;
-  memset(&fin, 0, sizeof(fin));
-  fin.ctl = a->ctl; fin.logstd = pf->p[pf->logstd]; fin.eps = eps; fin.A = pf->cfg.out_dim; fin.tanh_action = pf->cfg.tanh_action;
-  fin.t_plus1 = actor_t_plus1(a, s);
-  fin.acts_roll = acts_roll; fin.values_roll = values_roll; fin.logp_roll = logp_roll; fin.action = action;
-  fin.mean = mean; fin.stdv = stdv; fin.ent = ent; fin.value = value;
+  InfFinish fin = step_finish(a, io, s);
   g_op = "dense";
   if (!sw_on("V4L_ROLLOUT_DENSE_SPLIT")) {  // (read per call: tests switch it)
     // projector -> fc0 -> fc1 -> last linear -> epilogue as stages of one launch (device-side hand-overs)
@@ -2513,6 +2448,7 @@ static int run_actor_dense_cnn(v4l_actor* a, const float* obs, const float* eps,
   };
   head(0, pf, pk, h0p, ws_pf + Lp.out);
   head(1, vf, vk, h0v, ws_vf + Lv.out);
+  V4L_HIP_CHECK(lds_limit<&rollout_head_kernel<H>>(RollHeadLds::bytes));
   g_op = "head";
   V4L_KLAUNCH("rollout_head", 2.0 * 2 * E * (256 * 256 + 256 * 16), s, rollout_head_kernel<H>, dim3(2), dim3(512), RollHeadLds::bytes,
               s, hd, fin, E);
@@ -2521,23 +2457,11 @@ static int run_actor_dense_cnn(v4l_actor* a, const float* obs, const float* eps,
 }
 
 // state-only MLP nets, bf16: one launch per env step, one block per net for ALL E rows (csrc/rollout_dense.h rollout_mlp2_kernel)
-static bool actor_mlp2(const v4l_actor* a) {
-  const v4l_net_cfg& p = a->pf->cfg;
-  return is_half(p.compute) && a->E <= 64 && p.out_dim <= 16 && a->pf->enc[0].Kp == 128 && a->pf->enc[0].pkf >= 0 &&
-         a->pf->head[0].pkf >= 0 && a->vf->head[0].pkf >= 0;
-}
 template <typename H>
-static int run_actor_mlp2(v4l_actor* a, const float* obs, const float* eps, float* state_roll, float* acts_roll,
-                          float* values_roll, float* logp_roll, float* action, float* mean, float* stdv, float* ent, float* value,
-                          hipStream_t s) {
+static int run_actor_mlp2(v4l_actor* a, const StepIO& io, hipStream_t s) {
   v4l_net *pf = a->pf, *vf = a->vf;
   const int E = a->E;
-  static bool attr_done = false;
-  if (!attr_done) {
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_mlp2_kernel<H>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)RollMlp2Lds::bytes));
-    attr_done = true;
-  }
+  V4L_HIP_CHECK(lds_limit<&rollout_mlp2_kernel<H>>(RollMlp2Lds::bytes));
   const H* pk = (const H*)pf->packed;
   const H* vk = (const H*)vf->packed;
   const Layout Lp = pf->layout(E), Lv = vf->layout(E);
@@ -2554,32 +2478,17 @@ static int run_actor_mlp2(v4l_actor* a, const float* obs, const float* eps, floa
   };
   head(0, pf, pk, a->ws + Lp.out);
   head(1, vf, vk, a->ws + Lp.total + Lv.out);
-  InfFinish fin;
-  memset(&fin, 0, sizeof(fin));
-  fin.ctl = a->ctl; fin.logstd = pf->p[pf->logstd]; fin.eps = eps; fin.A = pf->cfg.out_dim; fin.tanh_action = pf->cfg.tanh_action;
-  fin.t_plus1 = actor_t_plus1(a, s);
-  fin.acts_roll = acts_roll; fin.values_roll = values_roll; fin.logp_roll = logp_roll; fin.action = action;
-  fin.mean = mean; fin.stdv = stdv; fin.ent = ent; fin.value = value;
+  const InfFinish fin = step_finish(a, io, s);
   g_op = "step";
   V4L_KLAUNCH("rollout_mlp", 2.0 * 2 * E * (128.0 * 256 + 4 * 256 * 256), s, rollout_mlp2_kernel<H>, dim3(2), dim3(1024),
-              RollMlp2Lds::bytes, s, obs, E, m, fin, state_roll);
+              RollMlp2Lds::bytes, s, io.obs, E, m, fin, io.state_roll);
   V4L_LAUNCH_CHECK();
   return 0;
 }
 
 // state-only MLP nets of the shipped shape: one launch per env step (rollout_mlp_kernel)
-static bool actor_fusable_mlp(const v4l_actor* a) {
-  const v4l_net_cfg &p = a->pf->cfg, &v = a->vf->cfg;
-  auto ok = [](const v4l_net_cfg& c) {
-    return c.kind == V4L_NET_MLP && c.n_enc_hidden == 2 && c.enc_hidden[0] == 256 && c.enc_hidden[1] == 256 &&
-           c.n_head_hidden == 2 && c.head_hidden[0] == 256 && c.head_hidden[1] == 256 && c.state_dim <= 128;
-  };
-  return ok(p) && ok(v);
-}
 template <typename T>
-static int run_actor_fused_mlp(v4l_actor* a, const float* obs, const float* eps, float* state_roll, float* acts_roll,
-                               float* values_roll, float* logp_roll, float* action, float* mean, float* stdv, float* ent,
-                               float* value, hipStream_t s) {
+static int run_actor_fused_mlp(v4l_actor* a, const StepIO& io, hipStream_t s) {
   v4l_net *pf = a->pf, *vf = a->vf;
   const int E = a->E;
   const T* pk = (const T*)pf->packed;
@@ -2600,176 +2509,117 @@ static int run_actor_fused_mlp(v4l_actor* a, const float* obs, const float* eps,
   };
   head(hd.n[0], pf, pk, ws_pf + Lp.out);
   head(hd.n[1], vf, vk, ws_vf + Lv.out);
-  InfFinish fin;
-  memset(&fin, 0, sizeof(fin));
-  fin.ctl = a->ctl; fin.logstd = pf->p[pf->logstd]; fin.eps = eps; fin.A = pf->cfg.out_dim; fin.tanh_action = pf->cfg.tanh_action;
-  fin.t_plus1 = actor_t_plus1(a, s);
-  fin.acts_roll = acts_roll; fin.values_roll = values_roll; fin.logp_roll = logp_roll; fin.action = action;
-  fin.mean = mean; fin.stdv = stdv; fin.ent = ent; fin.value = value;
+  const InfFinish fin = step_finish(a, io, s);
   g_op = "step";
   V4L_KLAUNCH("rollout_mlp", 2.0 * 2 * E * (128.0 * 256 + 4 * 256 * 256), s, rollout_mlp_kernel<T>, dim3(E, 2), dim3(1024), 0, s,
-              (const ActCtl*)a->ctl, obs, E, en, hd, fin, state_roll);
+              (const ActCtl*)a->ctl, io.obs, E, en, hd, fin, io.state_roll);
   V4L_LAUNCH_CHECK();
   return 0;
 }
 
+
+// The fused LocoTransformer step after its encoder: one sample per block and net (2E blocks of 8 waves), ALL layers, the heads, the
+// sampling of the action, the filing of action / value / log-prob at rollout slot t*E + i and the advance of the step cursor in
+// one launch. warm = 0: L2 warm-up touches at kernel entry measured +-0 (round 2), compiled out of the launch. xcd = 1: one net
+// per XCD half (see the kernel; the (E, 2) grid, where every XCD's L2 serves both nets, moved 6.1 MB of HBM traffic per launch
+// instead of 3.65 — round 4's A/B).
+template <typename T, int NT, int OPT>
+static int launch_roll_stack(hipStream_t s, int E, const InfLayerStack& stk, const InfHeadPair& hd, const InfFinish& fin) {
+  V4L_HIP_CHECK(lds_limit<&rollout_stack_kernel<T, 2, NT, OPT>>(RollStackLds<T>::bytes));
+  V4L_KLAUNCH("rollout_layers_head", 2.0 * 2 * E * (stk.nl * 872576.0 + 99840.0), s, (rollout_stack_kernel<T, 2, NT, OPT>),
+              dim3(2 * round_up(E, 4)), dim3(512), (RollStackLds<T>::bytes), s, stk, hd, fin, E, /*warm=*/0, /*xcd=*/1);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
+// Fused rollout step for the shipped LocoTransformer shape (csrc/infer.h): 2 launches instead of ~50. route: one of the STACK_*.
 template <typename T>
-static int run_actor_fused(v4l_actor* a, const float* obs, const float* eps, float* state_roll, void* image_roll,
-                           float* acts_roll, float* values_roll, float* logp_roll, float* action, float* mean, float* stdv,
-                           float* ent, float* value, hipStream_t s) {
+static int run_actor_fused(v4l_actor* a, const StepIO& io, StepRoute route, hipStream_t s) {
   typedef typename HalfOf<T>::type H;  // the fragment-pack encoder kernels exist for the 16-bit operand types only
   v4l_net *pf = a->pf, *vf = a->vf;
   const int E = a->E;
-  static bool attr_done = false;
-  if (!attr_done) {
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_encoder_kernel<T>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)InfEncLds<T>::bytes));
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_stack_kernel<T, 2>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)RollStackLds<T>::bytes));
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_stack_kernel<T, 2, 16>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)RollStackLds<T>::bytes));
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_encoder2_kernel<H, ENC_TOK16>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)RollEnc2Lds::bytes));
-    attr_done = true;
-  }
-  const bool vis = pf->cfg.kind == V4L_NET_LOCO_VIS;
   const T* pk = (const T*)pf->packed;
   const T* vk = (const T*)vf->packed;
   const Layout Lp = pf->layout(E), Lv = vf->layout(E);
   float* ws_pf = a->ws;
   float* ws_vf = a->ws + Lp.total;
   PhaseScope ps("rollout");
-  InfEnc en;
-  memset(&en, 0, sizeof(en));
-  en.w1 = pk + pf->conv[0].pk; en.w2 = pk + pf->conv[1].pk; en.w3 = pk + pf->conv[2].pk; en.wup = pk + pf->upconv.pk;
-  en.b1 = pf->p[pf->conv[0].b]; en.b2 = pf->p[pf->conv[1].b]; en.b3 = pf->p[pf->conv[2].b]; en.bup = pf->p[pf->upconv.b];
-  if (!vis) {
+  float* x0 = ws_pf + Lp.x[0];
+  g_op = "encoder";
+  if (route == StepRoute::STACK_F32ENC) {
+    InfEnc en;
+    memset(&en, 0, sizeof(en));
+    en.w1 = pk + pf->conv[0].pk; en.w2 = pk + pf->conv[1].pk; en.w3 = pk + pf->conv[2].pk; en.wup = pk + pf->upconv.pk;
+    en.b1 = pf->p[pf->conv[0].b]; en.b2 = pf->p[pf->conv[1].b]; en.b3 = pf->p[pf->conv[2].b]; en.bup = pf->p[pf->upconv.b];
     en.wf1 = pk + pf->enc[0].pk; en.wf2 = pk + pf->enc[1].pk; en.wpr = pk + pf->proj.pk;
     en.bf1 = pf->p[pf->enc[0].b]; en.bf2 = pf->p[pf->enc[1].b]; en.bpr = pf->p[pf->proj.b];
     en.Kp1 = pf->enc[0].Kp;
-  }
-  en.S = pf->cfg.state_dim; en.Sp = pf->Sp;
-  float* x0 = ws_pf + Lp.x[0];
-  g_op = "encoder";
-  if (vis) {  // 16 depth tokens, no proprio blocks (actor_fusable: bf16 only)
+    en.S = pf->cfg.state_dim; en.Sp = pf->Sp;
+    V4L_HIP_CHECK(lds_limit<&rollout_encoder_kernel<T>>(InfEncLds<T>::bytes));
+    V4L_KLAUNCH("rollout_encoder", 2.0 * E * 3678208.0, s, rollout_encoder_kernel<T>, dim3(E + cdiv(E, 32)), dim3(1024),
+                InfEncLds<T>::bytes, s, (const ActCtl*)a->ctl, io.obs, E, en, io.state_roll, (T*)io.image_roll, x0);
+  } else {
     const H* pb = (const H*)pf->packed;
     InfEncFrag ef;
     memset(&ef, 0, sizeof(ef));
     ef.w1 = pb + pf->conv[0].pkf; ef.w2 = pb + pf->conv[1].pkf; ef.w3 = pb + pf->conv[2].pkf; ef.wup = pb + pf->upconv.pkf;
-    ef.b1 = en.b1; ef.b2 = en.b2; ef.b3 = en.b3; ef.bup = en.bup;
-    ef.S = en.S; ef.Sp = en.Sp;
-    if (int rc = launch_encoder2<H, ENC_TOK16>(a, s, 2.0 * E * 3678208.0, dim3(E), obs, E, ef, state_roll, (H*)image_roll, x0,
-                                            (H*)nullptr, (H*)nullptr))
-      return rc;
-  } else if (sizeof(T) == 2 && pf->enc.size() == 2 && pf->enc[0].Kp == 128 && pf->conv[0].pkf >= 0) {
-    const H* pb = (const H*)pf->packed;
-    InfEncFrag ef;
-    ef.w1 = pb + pf->conv[0].pkf; ef.w2 = pb + pf->conv[1].pkf; ef.w3 = pb + pf->conv[2].pkf; ef.wup = pb + pf->upconv.pkf;
-    ef.b1 = en.b1; ef.b2 = en.b2; ef.b3 = en.b3; ef.bup = en.bup;
-    ef.wf1 = pb + pf->enc[0].pkf; ef.wf2 = pb + pf->enc[1].pkf; ef.wpr = pb + pf->proj.pkf;
-    ef.bf1 = en.bf1; ef.bf2 = en.bf2; ef.bpr = en.bpr;
-    ef.S = en.S; ef.Sp = en.Sp;
-    if (int rc = launch_encoder2<H, ENC_TOK17>(a, s, 2.0 * E * 3678208.0, dim3(E + cdiv(E, 32)), obs, E, ef, state_roll,
-                                            (H*)image_roll, x0, (H*)nullptr, (H*)nullptr))
-      return rc;
-  } else  // fp32 parity mode (fragments twice the size): weights streamed per wave
-    V4L_KLAUNCH("rollout_encoder", 2.0 * E * 3678208.0, s, rollout_encoder_kernel<T>, dim3(E + cdiv(E, 32)), dim3(1024),
-                InfEncLds<T>::bytes, s, (const ActCtl*)a->ctl, obs, E, en, state_roll, (T*)image_roll, x0);
+    ef.b1 = pf->p[pf->conv[0].b]; ef.b2 = pf->p[pf->conv[1].b]; ef.b3 = pf->p[pf->conv[2].b]; ef.bup = pf->p[pf->upconv.b];
+    ef.S = pf->cfg.state_dim; ef.Sp = pf->Sp;
+    if (route == StepRoute::STACK_TOK16) {  // 16 depth tokens, no proprio blocks
+      if (int rc = launch_encoder2<H, ENC_TOK16>(a, io, s, 2.0 * E * 3678208.0, dim3(E), ef, x0, (H*)nullptr, (H*)nullptr)) return rc;
+    } else {
+      ef.wf1 = pb + pf->enc[0].pkf; ef.wf2 = pb + pf->enc[1].pkf; ef.wpr = pb + pf->proj.pkf;
+      ef.bf1 = pf->p[pf->enc[0].b]; ef.bf2 = pf->p[pf->enc[1].b]; ef.bpr = pf->p[pf->proj.b];
+      if (int rc = launch_encoder2<H, ENC_TOK17>(a, io, s, 2.0 * E * 3678208.0, dim3(E + cdiv(E, 32)), ef, x0, (H*)nullptr,
+                                              (H*)nullptr))
+        return rc;
+    }
+  }
   V4L_LAUNCH_CHECK();
   const int nl = pf->cfg.n_layers;
-  const bool stack = true;  // actor_fusable(): two layers, fragment-order packs present
   auto fill = [&](InfLayer& d, v4l_net* net, const T* base, const TLayer& t, const float* xin, float* xout) {
-    d.win = base + t.inproj.pk; d.wo = base + t.outproj.pk; d.w1 = base + t.ff1.pk; d.w2 = base + t.ff2.pk;
-    if (stack) { d.win = base + t.inproj.pkf; d.wo = base + t.outproj.pkf; d.w1 = base + t.ff1.pkf; d.w2 = base + t.ff2.pkf; }
+    d.win = base + t.inproj.pkf; d.wo = base + t.outproj.pkf; d.w1 = base + t.ff1.pkf; d.w2 = base + t.ff2.pkf;
     d.bin = net->p[t.inproj.b]; d.bo = net->p[t.outproj.b]; d.b1 = net->p[t.ff1.b]; d.b2 = net->p[t.ff2.b];
     d.g1 = net->p[t.ln1.g]; d.be1 = net->p[t.ln1.b]; d.g2 = net->p[t.ln2.g]; d.be2 = net->p[t.ln2.b];
     d.xin = xin; d.xout = xout;
-    d.s_qkv = d.s_P = d.s_xh1 = d.s_rs1 = d.s_xh2 = d.s_rs2 = nullptr;
-    d.s_xin = d.s_ctx = d.s_x1 = d.s_f = nullptr;
   };
+  InfLayerStack stk;
+  memset(&stk, 0, sizeof(stk));
+  stk.nl = nl;
+  for (int l = 0; l < nl; ++l) {
+    fill(stk.l[l].n[0], pf, pk, pf->layers[l], l == 0 ? x0 : ws_pf + Lp.x[l], ws_pf + Lp.x[l + 1]);
+    fill(stk.l[l].n[1], vf, vk, vf->layers[l], l == 0 ? x0 : ws_vf + Lv.x[l], ws_vf + Lv.x[l + 1]);
+  }
   InfHeadPair hd;
   memset(&hd, 0, sizeof(hd));
-  InfFinish fin;
-  memset(&fin, 0, sizeof(fin));
   auto head = [&](InfHead& h, v4l_net* net, const T* base, float* out) {
-    h.w0 = base + net->head[0].pk; h.w1 = base + net->head[1].pk; h.w2 = base + net->head[2].pk;
-    if (stack) { h.w0 = base + net->head[0].pkf; h.w1 = base + net->head[1].pkf; h.w2 = base + net->head[2].pkf; }
+    h.w0 = base + net->head[0].pkf; h.w1 = base + net->head[1].pkf; h.w2 = base + net->head[2].pkf;
     h.b0 = net->p[net->head[0].b]; h.b1 = net->p[net->head[1].b]; h.b2 = net->p[net->head[2].b];
     h.out = out; h.nout = net->cfg.out_dim; h.max_pool = net->cfg.max_pool;
     if (net->cfg.token_norm) { h.tn_g = net->p[net->tok_ln.g]; h.tn_b = net->p[net->tok_ln.b]; }
     if (net->cfg.pytorch_encoder) { h.fn_g = net->p[net->fin_ln.g]; h.fn_b = net->p[net->fin_ln.b]; }
   };
-  auto finish = [&]() {
-    head(hd.n[0], pf, pk, ws_pf + Lp.out);
-    head(hd.n[1], vf, vk, ws_vf + Lv.out);
-    fin.ctl = a->ctl; fin.logstd = pf->p[pf->logstd]; fin.eps = eps; fin.A = pf->cfg.out_dim; fin.tanh_action = pf->cfg.tanh_action;
-  fin.t_plus1 = actor_t_plus1(a, s);
-    fin.acts_roll = acts_roll; fin.values_roll = values_roll; fin.logp_roll = logp_roll; fin.action = action;
-    fin.mean = mean; fin.stdv = stdv; fin.ent = ent; fin.value = value;
-  };
+  head(hd.n[0], pf, pk, ws_pf + Lp.out);
+  head(hd.n[1], vf, vk, ws_vf + Lv.out);
+  const InfFinish fin = step_finish(a, io, s);
   g_op = "layer";
-  {
-    // one sample per block and net (2E blocks of 8 waves): ALL layers, the heads, the sampling of the action, the filing
-    // of action / value / log-prob at rollout slot t*E + i and the advance of the step cursor in one launch
-    InfLayerStack stk;
-    memset(&stk, 0, sizeof(stk));
-    stk.nl = nl;
-    for (int l = 0; l < nl; ++l) {
-      fill(stk.l[l].n[0], pf, pk, pf->layers[l], l == 0 ? x0 : ws_pf + Lp.x[l], ws_pf + Lp.x[l + 1]);
-      fill(stk.l[l].n[1], vf, vk, vf->layers[l], l == 0 ? x0 : ws_vf + Lv.x[l], ws_vf + Lv.x[l + 1]);
-    }
-    finish();
-    constexpr int warm = 0;  // L2 warm-up touches at kernel entry: measured +-0 (round 2), compiled out of the launch
-    // one net per XCD half (see the kernel; the (E, 2) grid, where every XCD's L2 serves both nets, moved 6.1 MB of HBM traffic per
-    // launch instead of 3.65 — round 4's A/B)
-    constexpr int xcd = 1;
-    const dim3 grid = xcd ? dim3(2 * round_up(E, 4)) : dim3(E, 2);
-    // (token_norm / use_pytorch_encoder: the same kernel with the extra norm in front of / behind the layers; actor_fusable()
-    // admits one of the two, set alike on both nets)
-    const int opt = (pf->cfg.token_norm ? 1 : 0) | (pf->cfg.pytorch_encoder ? 2 : 0);
-#define V4L_ROLL_STACK(NT_, OPT_)                                                                                              \
-  do {                                                                                                                    \
-    static bool attr_ = false;                                                                                            \
-    if (!attr_) {                                                                                                         \
-      V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_stack_kernel<T, 2, NT_, OPT_>),            \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)RollStackLds<T>::bytes));       \
-      attr_ = true;                                                                                                       \
-    }                                                                                                                     \
-    V4L_KLAUNCH("rollout_layers_head", 2.0 * 2 * E * (nl * 872576.0 + 99840.0), s, (rollout_stack_kernel<T, 2, NT_, OPT_>), \
-                grid, dim3(512), (RollStackLds<T>::bytes), s, stk, hd, fin, E, warm, xcd);                                \
-  } while (0)
-    if (vis && opt == 1) V4L_ROLL_STACK(16, 1);
-    else if (vis && opt == 2) V4L_ROLL_STACK(16, 2);
-    else if (vis) V4L_ROLL_STACK(16, 0);
-    else if (opt == 1) V4L_ROLL_STACK(NTOK, 1);
-    else if (opt == 2) V4L_ROLL_STACK(NTOK, 2);
-    else V4L_ROLL_STACK(NTOK, 0);
-#undef V4L_ROLL_STACK
-    V4L_LAUNCH_CHECK();
+  const int opt = (pf->cfg.token_norm ? 1 : 0) | (pf->cfg.pytorch_encoder ? 2 : 0);
+  if (route == StepRoute::STACK_TOK16) {
+    if (opt == 1) return launch_roll_stack<T, 16, 1>(s, E, stk, hd, fin);
+    if (opt == 2) return launch_roll_stack<T, 16, 2>(s, E, stk, hd, fin);
+    return launch_roll_stack<T, 16, 0>(s, E, stk, hd, fin);
   }
-  return 0;
+  if (opt == 1) return launch_roll_stack<T, NTOK, 1>(s, E, stk, hd, fin);
+  if (opt == 2) return launch_roll_stack<T, NTOK, 2>(s, E, stk, hd, fin);
+  return launch_roll_stack<T, NTOK, 0>(s, E, stk, hd, fin);
 }
 
 
-// dynamic LDS of the loss launches that carry the heads' data-grad chain (85 KB in bf16: above the 64 KB default)
-template <typename T, int NW> static int loss_heads_attr() {
-  static bool done = false;
-  if (!done) {
-    const int bytes = (int)RowsChainLds<T, RowsChainCfg<T>::MT>::bytes3;
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&critic_loss_heads_kernel<T, NW>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    V4L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&actor_loss_heads_kernel<T, NW>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    done = true;
-  }
-  return 0;
-}
 // the loss launch with the heads' chain beside the statistics: grid = 1 + row blocks, NW waves per block
 template <typename T, int NW>
 static int launch_critic_loss_heads(hipStream_t s, const float* values, const float* ret, const float* oldv, const int* rowidx, int n,
                                     float inv_n, int clipped, float clip, float* dvalues, float* st, const RowsChain& hc, float gscale) {
-  int rc = loss_heads_attr<T, NW>();
-  if (rc) return rc;
+  // (the heads' data-grad chain: 85 KB of dynamic LDS in bf16, above the 64 KB default)
+  V4L_HIP_CHECK(lds_limit<&critic_loss_heads_kernel<T, NW>>(RowsChainLds<T, RowsChainCfg<T>::MT>::bytes3));
   V4L_KLAUNCH("critic_loss", 2.0 * n * (16 * 256 + 256 * 256 + 256 * 128), s, (critic_loss_heads_kernel<T, NW>),
               dim3(1 + cdiv(n, RowsChainCfg<T>::MT * 16)), dim3(NW * 64), (RowsChainLds<T, RowsChainCfg<T>::MT>::bytes3), s, values, ret,
               oldv, rowidx, n, inv_n, clipped, clip, dvalues, st, hc, gscale);
@@ -2777,8 +2627,7 @@ static int launch_critic_loss_heads(hipStream_t s, const float* values, const fl
 }
 template <typename T, int NW>
 static int launch_actor_loss_heads(hipStream_t s, const ActorArgs& aa, const RowsChain& hc) {
-  int rc = loss_heads_attr<T, NW>();
-  if (rc) return rc;
+  V4L_HIP_CHECK(lds_limit<&actor_loss_heads_kernel<T, NW>>(RowsChainLds<T, RowsChainCfg<T>::MT>::bytes3));
   V4L_KLAUNCH("actor_loss", 2.0 * aa.n * (16 * 256 + 256 * 256 + 256 * 128), s, (actor_loss_heads_kernel<T, NW>),
               dim3(1 + cdiv(aa.n, RowsChainCfg<T>::MT * 16)), dim3(NW * 64), (RowsChainLds<T, RowsChainCfg<T>::MT>::bytes3), s, aa, hc);
   return 0;
@@ -3219,45 +3068,27 @@ static bool actor_same_encoder_layout(const v4l_actor* a) {
   return same;
 }
 
-static int run_actor_step(v4l_actor* a, const float* obs, const float* eps, float* state_roll, void* image_roll,
-                          float* acts_roll, float* values_roll, float* logp_roll, float* action, float* mean, float* stdv,
-                          float* ent, float* value, int shared_encoder, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
+static int run_actor_step(v4l_actor* a, const StepIO& io, int shared_encoder, hipStream_t s) {
   v4l_net *pf = a->pf, *vf = a->vf;
   const int E = a->E;
   int rc;
   V4L_REQUIRE(pf->bound && vf->bound, "v4l_actor_step: nets are not bound");
-  // tanh_action policies (TanhNormal): the fused kernels' epilogues sample through tanh like act_finish_kernel (round 5),
-  // except the two-launch state-MLP and the dense NatureCNN kernels (rollout_dense.h) — such a policy takes the other fused family
-  const bool fused_ok = shared_encoder;
-  const bool tanh_pol = pf->cfg.tanh_action != 0;
-  if (fused_ok && actor_fusable_mlp(a) && pf->enc[0].Kp <= 128) {
-    if (actor_mlp2(a) && !tanh_pol)
-      return by_half(pf->cfg.compute, [&](auto tag) -> int {
-        return run_actor_mlp2<typename decltype(tag)::type>(a, obs, eps, state_roll, acts_roll, values_roll, logp_roll, action, mean,
-                                                            stdv, ent, value, s);
-      });
-    return by_compute(pf->cfg.compute, [&](auto tag) -> int {
-      return run_actor_fused_mlp<typename decltype(tag)::type>(a, obs, eps, state_roll, acts_roll, values_roll, logp_roll, action,
-                                                               mean, stdv, ent, value, s);
-    });
-  }
-  if (fused_ok && actor_dense_cnn(a) && !tanh_pol)
-    return by_half(pf->cfg.compute, [&](auto tag) -> int {
-      return run_actor_dense_cnn<typename decltype(tag)::type>(a, obs, eps, state_roll, image_roll, acts_roll, values_roll, logp_roll,
-                                                               action, mean, stdv, ent, value, s);
-    });
-  if (fused_ok && actor_fusable_cnn(a) && pf->enc[0].Kp <= 128) {
-    return by_compute(pf->cfg.compute, [&](auto tag) -> int {
-      return run_actor_fused_cnn<typename decltype(tag)::type>(a, obs, eps, state_roll, image_roll, acts_roll, values_roll, logp_roll,
-                                                               action, mean, stdv, ent, value, s);
-    });
-  }
-  if (fused_ok && actor_fusable(a)) {
-    return by_compute(pf->cfg.compute, [&](auto tag) -> int {
-      return run_actor_fused<typename decltype(tag)::type>(a, obs, eps, state_roll, image_roll, acts_roll, values_roll, logp_roll,
-                                                           action, mean, stdv, ent, value, s);
-    });
+  const int compute = pf->cfg.compute;
+  switch (const StepRoute route = step_route(a, shared_encoder)) {
+    case StepRoute::MLP_ONE_BLOCK:
+      return by_half(compute, [&](auto tag) -> int { return run_actor_mlp2<typename decltype(tag)::type>(a, io, s); });
+    case StepRoute::MLP_PER_SAMPLE:
+      return by_compute(compute, [&](auto tag) -> int { return run_actor_fused_mlp<typename decltype(tag)::type>(a, io, s); });
+    case StepRoute::CNN_DENSE:
+      return by_half(compute, [&](auto tag) -> int { return run_actor_dense_cnn<typename decltype(tag)::type>(a, io, s); });
+    case StepRoute::CNN_PER_SAMPLE:
+      return by_compute(compute, [&](auto tag) -> int { return run_actor_fused_cnn<typename decltype(tag)::type>(a, io, s); });
+    case StepRoute::STACK_TOK16:
+    case StepRoute::STACK_TOK17:
+    case StepRoute::STACK_F32ENC:
+      return by_compute(compute, [&](auto tag) -> int { return run_actor_fused<typename decltype(tag)::type>(a, io, route, s); });
+    case StepRoute::GENERAL:
+      break;
   }
   // General step. The value net may continue from the POLICY's encoder output (stage 2 reads enc_ws + its OWN layout's offset of
   // the token tensor) only if both nets lay their workspaces out identically up to that tensor: token_norm, use_pytorch_encoder
@@ -3274,7 +3105,7 @@ static int run_actor_step(v4l_actor* a, const float* obs, const float* eps, floa
   g_op = "ingest";
   if ((rc = by_compute(pf->cfg.compute, [&](auto tag) -> int {
         typedef typename decltype(tag)::type T;
-        V4L_KLAUNCH("ingest", 0, s, ingest_kernel<T>, dim3(E), dim3(256), 0, s, obs, E, S, pf->Sp, img, state_roll, (T*)image_roll,
+        V4L_KLAUNCH("ingest", 0, s, ingest_kernel<T>, dim3(E), dim3(256), 0, s, io.obs, E, S, pf->Sp, img, io.state_roll, (T*)io.image_roll,
                     (int64_t)0, (const long long*)&a->ctl->t);
         V4L_LAUNCH_CHECK();
         return 0;
@@ -3282,13 +3113,12 @@ static int run_actor_step(v4l_actor* a, const float* obs, const float* eps, floa
     return rc;
   float* ws_pf = a->ws;
   float* ws_vf = a->ws + pf->layout(E).total;
-  V4L_REQUIRE(pf->bound && vf->bound, "v4l_actor_step: nets are not bound");
   // policy encoder, then the two trunks side by side: the value net shares the encoder with the policy
   // (starter/ppo_locotransformer.py:79-100) and continues from the policy's token tensor on the aux stream
   auto fwd = [&](v4l_net* net, float* ws, hipStream_t st, const float* enc, int stage) {
     return by_compute(pf->cfg.compute, [&](auto tag) -> int {
       typedef typename decltype(tag)::type T;
-      return net->forward_t<T>(state_roll, (const T*)image_roll, a->rowidx, E, ws, st, enc, stage);
+      return net->forward_t<T>(io.state_roll, (const T*)io.image_roll, a->rowidx, E, ws, st, enc, stage);
     });
   };
   const bool par = shared_encoder && a->aux != nullptr && !capturing(s);
@@ -3312,39 +3142,24 @@ static int run_actor_step(v4l_actor* a, const float* obs, const float* eps, floa
   }
   g_op = "sample";
   V4L_KLAUNCH("act_finish", 0, s, act_finish_kernel, dim3(1), dim3(256), 0, s, a->ctl, ws_pf + pf->layout(E).out,
-              pf->p[pf->logstd], ws_vf + vf->layout(E).out, eps, E, pf->cfg.out_dim, acts_roll, values_roll, logp_roll, action,
-              mean, stdv, ent, value, pf->cfg.tanh_action);
+              pf->p[pf->logstd], ws_vf + vf->layout(E).out, io.eps, E, pf->cfg.out_dim, io.acts_roll, io.values_roll, io.logp_roll,
+              io.action, io.mean, io.stdv, io.ent, io.value, pf->cfg.tanh_action);
   V4L_LAUNCH_CHECK();
   return 0;
 }
 
-static int actor_step_impl(v4l_actor* a, const float* obs_dev, const float* eps_dev, float* state_roll_dev, void* image_roll_dev,
-                           float* acts_roll_dev, float* values_roll_dev, float* logp_roll_dev, float* action_dev, float* mean_dev,
-                           float* std_dev, float* ent_dev, float* value_dev, int shared_encoder, int use_graph, void* stream);
-int v4l_actor_step(v4l_actor* a, const float* obs_dev, const float* eps_dev, float* state_roll_dev, void* image_roll_dev,
-                   float* acts_roll_dev, float* values_roll_dev, float* logp_roll_dev, float* action_dev, float* mean_dev,
-                   float* std_dev, float* ent_dev, float* value_dev, int shared_encoder, int use_graph, void* stream) {
-  const int rc = actor_step_impl(a, obs_dev, eps_dev, state_roll_dev, image_roll_dev, acts_roll_dev, values_roll_dev, logp_roll_dev,
-                                 action_dev, mean_dev, std_dev, ent_dev, value_dev, shared_encoder, use_graph, stream);
-  if (rc == 0 && a->t_host >= 0) ++a->t_host;  // one env step, whichever way it was launched (the device cursor moved too)
-  return rc;
-}
-static int actor_step_impl(v4l_actor* a, const float* obs_dev, const float* eps_dev, float* state_roll_dev, void* image_roll_dev,
-                           float* acts_roll_dev, float* values_roll_dev, float* logp_roll_dev, float* action_dev, float* mean_dev,
-                           float* std_dev, float* ent_dev, float* value_dev, int shared_encoder, int use_graph, void* stream) {
+static int actor_step_impl(v4l_actor* a, const StepIO& io, int shared_encoder, int use_graph, hipStream_t s) {
   V4L_REQUIRE(a && a->bound, "v4l_actor_step: actor is not bound");
-  V4L_REQUIRE(obs_dev && eps_dev && state_roll_dev && action_dev && mean_dev && std_dev && ent_dev && value_dev,
+  V4L_REQUIRE(io.obs && io.eps && io.state_roll && io.action && io.mean && io.stdv && io.ent && io.value,
               "v4l_actor_step: null argument");
-  V4L_REQUIRE(a->pf->cfg.kind == V4L_NET_MLP || image_roll_dev, "v4l_actor_step: image rollout array missing");
-  hipStream_t s = (hipStream_t)stream;
-  auto run = [&]() {
-    return run_actor_step(a, obs_dev, eps_dev, state_roll_dev, image_roll_dev, acts_roll_dev, values_roll_dev, logp_roll_dev,
-                          action_dev, mean_dev, std_dev, ent_dev, value_dev, shared_encoder, stream);
-  };
+  V4L_REQUIRE(a->pf->cfg.kind == V4L_NET_MLP || io.image_roll, "v4l_actor_step: image rollout array missing");
+  auto run = [&]() { return run_actor_step(a, io, shared_encoder, s); };
   if (!use_graph || g_prof || s == nullptr) return run();
-  const void* key[16] = {obs_dev, eps_dev, state_roll_dev, image_roll_dev, acts_roll_dev, values_roll_dev, action_dev,
-                         mean_dev, logp_roll_dev, ent_dev, value_dev, (const void*)(intptr_t)(shared_encoder + 1), std_dev,
-                         (const void*)(intptr_t)a->pf->gen, (const void*)(intptr_t)a->vf->gen, nullptr};
+  // (a captured step reads fp32 rows: img16 is null here)
+  const void* key[16] = {io.obs, io.eps, io.state_roll, io.image_roll, io.acts_roll, io.values_roll, io.logp_roll, io.action,
+                         io.mean, io.stdv, io.ent, io.value, io.img16, (const void*)(intptr_t)(shared_encoder + 1),
+                         (const void*)(intptr_t)a->pf->gen, (const void*)(intptr_t)a->vf->gen};
+  static_assert(sizeof(key) == sizeof(a->key), "graph key size");
   if (memcmp(key, a->key, sizeof(key)) != 0) {
     if (a->gexec) { (void)hipGraphExecDestroy(a->gexec); a->gexec = nullptr; }
     a->warm = false;
@@ -3371,17 +3186,25 @@ static int actor_step_impl(v4l_actor* a, const float* obs_dev, const float* eps_
   V4L_TRACE("actor: launched");
   return 0;
 }
+static int actor_step(v4l_actor* a, const StepIO& io, int shared_encoder, int use_graph, void* stream) {
+  const int rc = actor_step_impl(a, io, shared_encoder, use_graph, (hipStream_t)stream);
+  if (rc == 0 && a->t_host >= 0) ++a->t_host;  // one env step, whichever way it was launched (the device cursor moved too)
+  return rc;
+}
+int v4l_actor_step(v4l_actor* a, const float* obs_dev, const float* eps_dev, float* state_roll_dev, void* image_roll_dev,
+                   float* acts_roll_dev, float* values_roll_dev, float* logp_roll_dev, float* action_dev, float* mean_dev,
+                   float* std_dev, float* ent_dev, float* value_dev, int shared_encoder, int use_graph, void* stream) {
+  const StepIO io = {obs_dev, eps_dev, state_roll_dev, image_roll_dev, acts_roll_dev, values_roll_dev, logp_roll_dev, action_dev,
+                     mean_dev, std_dev, ent_dev, value_dev, nullptr, 0};
+  return actor_step(a, io, shared_encoder, use_graph, stream);
+}
 
-// Which actors run their step on rollout_encoder2_kernel — the kernels that can take the observation split (the dispatch order
-// of run_actor_step)
+// Which actors' steps take the observation split: the routes on rollout_encoder2_kernel (they imply a shared encoder, 16-bit
+// compute and an image net). A TanhNormal policy keeps the fp32 rows, even on a LocoTransformer route that could read the split.
 static bool actor_takes_split(const v4l_actor* a, int shared_encoder) {
-  const v4l_net* pf = a->pf;
-  if (!shared_encoder || pf->cfg.tanh_action || !is_half(pf->cfg.compute) || pf->cfg.kind == V4L_NET_MLP) return false;
-  if (actor_dense_cnn(a)) return true;
-  if (actor_fusable_cnn(a) && pf->enc[0].Kp <= 128) return false;  // the per-sample rollout_cnn_kernel reads fp32 rows
-  if (!actor_fusable(a)) return false;
-  if (pf->cfg.kind == V4L_NET_LOCO_VIS) return true;
-  return pf->enc.size() == 2 && pf->enc[0].Kp == 128 && pf->conv[0].pkf >= 0;
+  if (a->pf->cfg.tanh_action) return false;
+  const StepRoute r = step_route(a, shared_encoder);
+  return r == StepRoute::CNN_DENSE || r == StepRoute::STACK_TOK16 || r == StepRoute::STACK_TOK17;
 }
 int v4l_actor_split_supported(const v4l_actor* a, int shared_encoder) {
   return (a && a->bound && actor_takes_split(a, shared_encoder)) ? 1 : 0;
@@ -3395,14 +3218,12 @@ int v4l_actor_step_split(v4l_actor* a, const float* proprio_dev, const void* ima
               "v4l_actor_step_split: this actor's step does not run on the split-observation kernels (bf16 compute, an image "
               "net on the fused rollout step); use v4l_actor_step with fp32 observation rows");
   V4L_REQUIRE(proprio_dev != nullptr || a->pf->cfg.state_dim == 0, "v4l_actor_step_split: proprio rows missing");
-  a->img16 = image16_dev;
-  a->ld_img16 = (int64_t)a->pf->cfg.in_channels * a->pf->cfg.img_hw * a->pf->cfg.img_hw;
-  // (vision-only nets, S = 0: no kernel reads the row pointer; the argument check of v4l_actor_step wants it non-null)
+  // (vision-only nets, S = 0: no kernel reads the row pointer; the argument check of the step wants it non-null)
   const float* rows = proprio_dev != nullptr ? proprio_dev : reinterpret_cast<const float*>(image16_dev);
-  const int rc = v4l_actor_step(a, rows, eps_dev, state_roll_dev, image_roll_dev, acts_roll_dev, values_roll_dev, logp_roll_dev,
-                                action_dev, mean_dev, std_dev, ent_dev, value_dev, shared_encoder, /*use_graph=*/0, stream);
-  a->img16 = nullptr;
-  return rc;
+  const StepIO io = {rows, eps_dev, state_roll_dev, image_roll_dev, acts_roll_dev, values_roll_dev, logp_roll_dev, action_dev,
+                     mean_dev, std_dev, ent_dev, value_dev, image16_dev,
+                     (int64_t)a->pf->cfg.in_channels * a->pf->cfg.img_hw * a->pf->cfg.img_hw};
+  return actor_step(a, io, shared_encoder, /*use_graph=*/0, stream);
 }
 
 // ---- the collector's env step as one host call (csrc/host_step.h)
