@@ -496,6 +496,30 @@ class HipTrainer:
       self._steps_on_device = False
     return self._adam_steps
 
+  def adam_state(self):
+    """-> (m_pf, v_pf, m_vf, v_vf, (pf steps, vf steps)): the four flat moment buffers (views, plan order: HipNet.grad_offsets)
+    and the committed step counts. Everything of the optimisers that outlives a run: the rest of the control block is rewritten
+    by begin(). Waits for the device, so the views are current (after a guarded run adam_steps() reads the counts back anyway)."""
+    steps = self.adam_steps()
+    torch.cuda.synchronize(self.device)
+    return self.m_pf, self.v_pf, self.m_vf, self.v_vf, steps
+
+  def load_adam_state(self, m_pf=None, v_pf=None, m_vf=None, v_vf=None, steps=(None, None), updates=None):
+    """The inverse of adam_state(), in place: the moment buffers keep their addresses (the captured update graph is keyed on them)
+    and the counts go to the device with the next begin() — through v4l_trainer_begin_guarded whenever they differ. None keeps a
+    buffer / a count as it is (the optimiser facades load one side each). updates: minibatch updates run so far (`step`); default:
+    the larger count."""
+    cur = self.adam_steps()
+    for dst, src in ((self.m_pf, m_pf), (self.v_pf, v_pf), (self.m_vf, m_vf), (self.v_vf, v_vf)):
+      if src is not None:
+        if src.numel() != dst.numel():
+          raise ValueError("vision4leg_amd: moment buffer has %d elements, the trainer's has %d" % (src.numel(), dst.numel()))
+        dst.copy_(src.reshape(-1).to(torch.float32))
+    torch.cuda.synchronize(self.device)
+    self._adam_steps = tuple(int(c if s is None else s) for s, c in zip(steps, cur))
+    self._steps_on_device = False
+    self.step = int(updates) if updates is not None else max(self._adam_steps)
+
   def _count(self, updates):
     self.step += updates
     if self._guarded:

@@ -25,15 +25,18 @@ import torch
 from .. import utils as atu
 from ... import replay_buffers as rb
 from .... import _lib
+from .... import train_state as ts
 from ....engine import HipTrainer
 
 
 class _HipAdam:
-    """Optimiser facade: the Adam state lives in the trainer's flat device buffers; this object only carries
-    the learning rate so `update_linear_schedule` and user code can read/write `param_groups[0]['lr']`."""
+    """Optimiser facade: the Adam state lives in the trainer's flat device buffers; this object carries the learning rate so
+    `update_linear_schedule` and user code can read/write `param_groups[0]['lr']`, and — once PPO has attached the trainer —
+    reads and writes that state in `torch.optim.Adam`'s own `state_dict()` format (vision4leg_amd/train_state.py)."""
 
     def __init__(self, params, lr, eps=1e-5, betas=(0.9, 0.999)):
         self.param_groups = [{"params": list(params), "lr": lr, "eps": eps, "betas": betas, "weight_decay": 0}]
+        self._trainer = None
 
     @property
     def lr(self):
@@ -41,6 +44,52 @@ class _HipAdam:
 
     def zero_grad(self):
         pass
+
+    def attach(self, trainer, side, module):
+        """side: 0 = the trainer's pf buffers and count, 1 = vf's; module: the net whose parameters() this optimiser owns."""
+        self._trainer, self._side, self._module = trainer, side, module
+
+    def _slices(self):
+        if self._trainer is None:
+            raise RuntimeError("vision4leg_amd: this optimiser facade is not attached to a trainer (PPO.__init__ does that)")
+        net = self._trainer.vf if self._side else self._trainer.pf
+        return net, ts.param_slices(net, self._module)
+
+    def state_dict(self):
+        """What `torch.optim.Adam(net.parameters(), lr=..., eps=1e-5).state_dict()` would hold after the same steps."""
+        _, slices = self._slices()
+        state = self._trainer.adam_state()
+        g = self.param_groups[0]
+        return ts.export_adam(slices, state[2 * self._side], state[2 * self._side + 1], state[4][self._side], g["lr"], g["betas"], g["eps"])
+
+    def load_state_dict(self, sd):
+        """From this class or from a real `torch.optim.Adam` over the same module. Moments go into the trainer's buffers in
+        place, the step count to the host side (the next begin() hands it to the device), `lr` into the param group."""
+        net, slices = self._slices()
+        m, v, step, group = ts.import_adam(slices, sd, net.total_params)
+        g = self.param_groups[0]
+        if "betas" in group and tuple(float(b) for b in group["betas"]) != tuple(float(b) for b in g["betas"]) \
+                or "eps" in group and float(group["eps"]) != float(g["eps"]):
+            raise ValueError("vision4leg_amd: the optimiser state was written with betas %s / eps %s, the HIP engine runs %s / %s"
+                             % (group.get("betas"), group.get("eps"), g["betas"], g["eps"]))
+        if self._side:
+            self._trainer.load_adam_state(m_vf=m, v_vf=v, steps=(None, step))
+        else:
+            self._trainer.load_adam_state(m_pf=m, v_pf=v, steps=(step, None))
+        g["lr"] = float(group["lr"])
+
+
+class _StartEpoch(int):
+    """`PPO.start_epoch`: the first epoch `train()` runs (0, or the checkpoint's epoch + 1 after `load_checkpoint`) — and, called,
+    still the reference's per-epoch hook of that name (rl_algo.py:72-73, 103, 109), which subclasses may override."""
+
+    def __new__(cls, value, hook):
+        self = super().__new__(cls, value)
+        self._hook = hook
+        return self
+
+    def __call__(self):
+        return self._hook()
 
 
 def _dist_world():
@@ -131,7 +180,7 @@ class PPO:
                  opt_epochs=10, clipped_value_loss=False, shuffle=True, tau=None, gae=True, env=None,
                  replay_buffer=None, collector=None, logger=None, grad_clip=None, discount=0.99, num_epochs=3000,
                  batch_size=128, device="cpu", save_interval=100, eval_interval=1, save_dir=None, skip_nonfinite_steps=False,
-                 **kwargs):
+                 save_train_state=False, resume=None, **kwargs):
         if optimizer_class is not None and optimizer_class is not torch.optim.Adam:
             raise NotImplementedError("vision4leg_amd: PPO runs Adam on the HIP engine; optimizer_class must be Adam")
         self.device = torch.device(device)
@@ -177,6 +226,12 @@ class PPO:
         self.clipped_value_loss = clipped_value_loss
         self.sample_key = ["obs", "acts", "advs", "estimate_returns", "values"]
         self.current_epoch = 0
+        # resumable training state. save_train_state (config "save_train_state": true): the save_interval and
+        # "finish" saves of train() also write train_state_{epoch}.pth; resume (config "resume"): a directory (its newest numbered
+        # train_state file) or (directory, epoch) to continue from, loaded at the end of this constructor.
+        self.save_train_state = bool(save_train_state)
+        self.total_frames = 0
+        self.start_epoch = _StartEpoch(0, type(self).start_epoch.__get__(self))
         # opt-in (config "skip_nonfinite_steps": true): an optimiser step whose gradient norm is not finite is skipped on the
         # device — parameters, Adam moments and that optimiser's step count untouched, like torch.cuda.amp.GradScaler.step —
         # instead of writing NaN and raising after the epoch. Off (the reference's behaviour): step, then raise.
@@ -228,6 +283,16 @@ class PPO:
         elif replay_buffer is not None:
             replay_buffer.gae_device = self.device
         self._stage = None
+        self.pf_optimizer.attach(self.trainer, 0, self.pf)
+        self.vf_optimizer.attach(self.trainer, 1, self.vf)
+        if resume is not None:
+            if isinstance(resume, (str, os.PathLike)):
+                prefix, epoch = os.fspath(resume), ts.newest(resume)
+                if epoch is None:
+                    raise FileNotFoundError("vision4leg_amd: resume=%r holds no train_state_<epoch>.pth" % (resume,))
+            else:
+                prefix, epoch = resume
+            self.load_checkpoint(prefix, epoch)
 
     # ---- data-parallel bootstrap ---------------------------------------------------------------------
     def _agree(self, ok):
@@ -343,6 +408,126 @@ class PPO:
                 pickle.dump(norm, f)
         for name, network in self.snapshot_networks:
             torch.save(network.state_dict(), osp.join(prefix, "model_{}_{}.pth".format(name, epoch)))
+
+    # ---- resumable training state --------------------------------------------------------
+    def train_state(self):
+        """Everything of a run that the model files do not hold and that the process would take with it, as tensors, numbers,
+        strings, lists and dicts (what torch.load(weights_only=True) reads). Reads the Adam moments back: one synchronise."""
+        from ....engine import COMPUTE_NAMES
+        coll = self.collector
+        with torch.cuda.device(self.device):
+            cuda_rng = torch.cuda.get_rng_state(self.device)
+            return {
+                "format_version": ts.FORMAT_VERSION,
+                "pf_optimizer": self.pf_optimizer.state_dict(),
+                "vf_optimizer": self.vf_optimizer.state_dict(),
+                "epoch": int(self.current_epoch),  # the last completed epoch
+                "total_frames": int(self.total_frames),
+                "training_update_num": int(self.training_update_num),
+                "best_eval": None if self.best_eval is None else float(self.best_eval),
+                "episode_rewards": ts.plain_rewards(self.episode_rewards),
+                "training_episode_rewards": ts.plain_rewards(self.training_episode_rewards),
+                "skipped_steps": {k: int(v) for k, v in self.skipped_steps.items()},
+                "f16_saturated": float(self.f16_saturated),
+                "compute": COMPUTE_NAMES[self.pf.hip.compute],
+                "net_kinds": {"pf": int(self.pf.hip.kind), "vf": int(self.vf.hip.kind)},
+                "rng": {"numpy": ts.pack_numpy_rng(), "torch_cpu": torch.get_rng_state(), "torch_cuda": cuda_rng},
+                "collector": {"current_step": ts.optional_tensor(getattr(coll, "current_step", None)),
+                              "train_rew": ts.optional_tensor(getattr(coll, "train_rew", None))},
+            }
+
+    def save_checkpoint(self, prefix, epoch):
+        """snapshot(prefix, epoch) — the reference's files, names and contents unchanged — plus train_state_{epoch}.pth: both
+        optimisers in torch.optim.Adam's state_dict format, the schedule position, counters and RNG streams. Data parallel:
+        every rank reads its state back (the ranks hold the same), rank 0 writes."""
+        state = self.train_state()
+        if self.world_size > 1 and torch.distributed.get_rank() != 0:
+            return
+        self.snapshot(prefix, epoch)
+        tmp = ts.path(prefix, epoch) + ".tmp"
+        torch.save(state, tmp)
+        os.replace(tmp, ts.path(prefix, epoch))  # a process killed while writing leaves the previous file whole
+
+    def _check_model_file(self, name, network, sd, state):
+        """A checkpoint of another net geometry: raise with the first mismatching parameter, before anything is overwritten."""
+        have = {k: tuple(v.shape) for k, v in network.state_dict().items()}
+        got = {k: tuple(v.shape) for k, v in sd.items()}
+        bad = next((k for k in got if have.get(k) != got[k]), None) or next((k for k in have if k not in got), None)
+        if bad is not None:
+            raise RuntimeError("vision4leg_amd: checkpoint does not fit this %s net: parameter %s is %s in the file and %s here "
+                               "(file: net kinds %s, compute %s; here: kind %d)"
+                               % (name, bad, got.get(bad, "missing"), have.get(bad, "missing"), state.get("net_kinds"),
+                                  state.get("compute"), network.hip.kind))
+
+    def load_checkpoint(self, prefix, epoch, restore_rng=True, restore_collector=False):
+        """Continue from save_checkpoint(prefix, epoch): parameters, both Adam moment sets and step counts, the schedule position
+        (train() goes on at the file's epoch + 1), counters and — restore_rng — numpy's, torch's CPU and this device's generator
+        states. A file written in another compute mode loads (the masters are fp32); another net geometry raises. The simulator
+        is not part of the file: the run goes on from env.reset(), which is why the collector's per-episode step counts and
+        partial returns are in the file but only put back on request (restore_collector: for a caller that restores its env)."""
+        state = ts.load(prefix, epoch)
+        files = {}
+        for name, network in self.snapshot_networks:
+            files[name] = torch.load(osp.join(prefix, "model_{}_{}.pth".format(name, epoch)), map_location="cpu", weights_only=True)
+            self._check_model_file(name, network, files[name], state)
+        with torch.cuda.device(self.device):
+            for name, network in self.snapshot_networks:
+                network.load_state_dict(files[name])
+            atu.copy_model_params_from_to(self.pf, self.target_pf)
+            for net in self.networks:
+                net.mark_params_changed()
+            self._load_normalizer(osp.join(prefix, "_obs_normalizer_{}.pkl".format(epoch)))
+            self.pf_optimizer.load_state_dict(state["pf_optimizer"])
+            self.vf_optimizer.load_state_dict(state["vf_optimizer"])
+            self.training_update_num = int(state["training_update_num"])
+            self.trainer.step = self.training_update_num  # updates run, skipped steps included
+            if self.world_size > 1:
+                self._agree_on_adam_state()
+            if restore_rng:
+                np.random.set_state(ts.unpack_numpy_rng(state["rng"]["numpy"]))
+                torch.set_rng_state(state["rng"]["torch_cpu"])
+                torch.cuda.set_rng_state(state["rng"]["torch_cuda"], self.device)
+        self.total_frames = int(state["total_frames"])
+        self.best_eval = state["best_eval"]
+        self.episode_rewards = deque(ts.restore_rewards(state["episode_rewards"]), maxlen=30)
+        self.training_episode_rewards = deque(ts.restore_rewards(state["training_episode_rewards"]), maxlen=30)
+        self.skipped_steps = {k: int(v) for k, v in state["skipped_steps"].items()}
+        if state["f16_saturated"]:
+            self.f16_saturated = float(state["f16_saturated"])
+        if restore_collector:
+            for key, value in state["collector"].items():
+                if value is not None:
+                    setattr(self.collector, key, value.numpy().copy())
+        self.current_epoch = int(state["epoch"])
+        self.start_epoch = _StartEpoch(self.current_epoch + 1, self.start_epoch._hook)
+        return state
+
+    def _load_normalizer(self, path):
+        norm = getattr(self.env, "_obs_normalizer", None)
+        if norm is None or not osp.exists(path):
+            return
+        with open(path, "rb") as f:  # written by snapshot(): this package's or the reference's Normalizer
+            saved = pickle.load(f)
+        if hasattr(norm, "load_state"):  # the device-resident normaliser: in place, its buffers keep their addresses
+            norm.load_state(saved.state() if hasattr(saved, "state") else type(norm).from_reference(saved, norm.device).state())
+        else:
+            self.env._obs_normalizer = saved
+
+    def _agree_on_adam_state(self):
+        """Data parallel: every rank read the file itself; one MIN all-reduce over [x | -x] (min and -max of each entry) shows
+        whether the step counts and a sum over the loaded moments are the same on all ranks. Raises on every rank if not."""
+        dist = torch.distributed
+        m_pf, v_pf, m_vf, v_vf, steps = self.trainer.adam_state()
+        x = torch.stack([torch.tensor(float(s), dtype=torch.float64, device=self.device) for s in steps]
+                        + [b.double().sum() for b in (m_pf, v_pf, m_vf, v_vf)])
+        t = torch.cat([x, -x])
+        if dist.get_backend() != "nccl":
+            t = t.cpu()
+        dist.all_reduce(t, op=dist.ReduceOp.MIN)
+        lo, hi = t[:6], -t[6:]
+        if not torch.equal(lo, hi):
+            raise RuntimeError("vision4leg_amd: the ranks loaded different optimiser states (step counts / moment sums, smallest "
+                               "%s, largest %s)" % (lo.tolist(), hi.tolist()))
 
     # ---- epoch ---------------------------------------------------------------------------------------
     def process_epoch_samples(self):
@@ -521,9 +706,11 @@ class PPO:
     # ---- outer loop (rl_algo.py:97-168) ----------------------------------------------------------------
     def train(self):
         self.pretrain()
-        total_frames = getattr(self, "pretrain_frames", 0)
+        first = int(self.start_epoch)  # 0, or the epoch after a loaded checkpoint's (load_checkpoint)
+        total_frames = self.total_frames if first else getattr(self, "pretrain_frames", 0)
+        save = self.save_checkpoint if self.save_train_state else self.snapshot
         self.start_epoch()
-        for epoch in range(self.num_epochs):
+        for epoch in range(first, self.num_epochs):
             self.current_epoch = epoch
             self.start_epoch()
             t0 = time.time()
@@ -537,6 +724,7 @@ class PPO:
             self.train_time += time.time() - t0
             finish_epoch_info = self.finish_epoch()
             total_frames += self.epoch_frames
+            self.total_frames = total_frames
             if epoch % self.eval_interval == 0:
                 t0 = time.time()
                 eval_infos = self.collector.eval_one_epoch()
@@ -563,6 +751,6 @@ class PPO:
                 self.logger.add_epoch_info(epoch, total_frames, time.time() - self.start, infos)
                 self.start = time.time()
             if epoch % self.save_interval == 0:
-                self.snapshot(self.save_dir, epoch)
-        self.snapshot(self.save_dir, "finish")
+                save(self.save_dir, epoch)
+        save(self.save_dir, "finish")
         self.collector.terminate()
