@@ -81,6 +81,38 @@ struct Layout {
   int64_t total = 0;
 };
 
+// The kernels that run the Transformer layers of a training pass (v4l_net::layer_route), forward and backward alike
+enum class LayerFamily {
+  NONE,             // state MLP / NatureCNN nets: no Transformer layers
+  WPS_PLAIN,        // the shipped LocoTransformer (mean or max pooling): wps_layer_fwd_kernel / wps_layer_bwd_kernel, or the two
+                    // as wps_layer_fb_kernel when the trainer hands the loss over (fb_allowed)
+  WPS_VIS,          // vision-only net: the same pair, native 16-token instantiation (VIS = 2)
+  WPS_VIS17,        // vision-only net, V4L_VIS17 / V4L_LAYER_TAPS: the 17-row instantiation (dummy row 0)
+  WPS_OPT,          // token_norm / use_pytorch_encoder / another proprio MLP: the wave-per-sample pair (MODE 1..3) between
+                    // layer-by-layer launches (token_ln; the final norm + pooling + heads; the encoder-side data-grads)
+  WPS_OPT_VIS,      // the same for the vision-only net (VIS = 2 over 17-row slots)
+  BLOCK_STACK,      // infer_layer_kernel<.., NL = 2>; bwd_layer_kernel<.., NL = 2> (NL = 1 twice unless tail_in)
+  BLOCK_PER_LAYER,  // infer_layer_kernel / bwd_layer_kernel, NL = 1: one launch per layer, heads / tail riding on the outer ones
+  LAYER_BY_LAYER,   // GEMM + attention + LayerNorm launches (lin_fwd, attn_fwd_kernel, add_ln_fwd_kernel and their backwards)
+};
+struct LayerRoute {
+  LayerFamily family = LayerFamily::NONE;
+  bool heads_in = false;  // the pooled heads run inside the layers' launch (else: final norm / pooling / head chain launches)
+  bool tail_in = false;   // the encoder-side data-grads (proprio MLP + projector, up-conv) come out of the layers' launch
+  bool rows17 = false;    // vision-only net on the wave-per-sample kernels: its 16 tokens sit in rows 1..16 of 17-row slots
+  bool fb_allowed = false;         // the trainer may hand the loss over for the fused forward-loss-backward launch (V4L_NO_FB: never)
+  bool heads_ext_allowed = false;  // ... may run the policy's pooled-heads data-grad chain beside the loss statistics
+  bool heads_ext_critic = false;   // ... and the critic's (V4L_WPS_HEAD_EXT_CRITIC)
+  // diagnostic switches, read once per pass
+  bool taps = false;      // V4L_LAYER_TAPS: the kernels also write every intermediate (tests)
+  bool stack_ok = true;   // !V4L_NO_LAYER_STACK
+  bool tok0_in = false;   // V4L_WPS_TOK0_IN: the proprio branch's data-grad chain stays inside the backward launch
+  int par_wgrad = 2;      // V4L_PAR_WGRAD: schedule of the weight-grad section (backward_t)
+  bool wps() const { return family >= LayerFamily::WPS_PLAIN && family <= LayerFamily::WPS_OPT_VIS; }
+  bool opt() const { return family == LayerFamily::WPS_OPT || family == LayerFamily::WPS_OPT_VIS; }
+  bool block() const { return family == LayerFamily::BLOCK_STACK || family == LayerFamily::BLOCK_PER_LAYER; }
+};
+
 }  // namespace v4l
 
 struct v4l_net {
@@ -149,24 +181,22 @@ struct v4l_net {
   // stage: 0 = whole net, 1 = encoder only (up to the token / concat tensor), 2 = trunk + head only
   template <typename T> int forward_t(const float* state, const T* image, const int* rowidx, int n, float* ws, hipStream_t s,
                                       const float* enc_ws = nullptr, int stage = 0);
+  // Which kernels run the Transformer layers of a training pass: decided here, once, for forward_t, backward_t, heads_ext and
+  // the trainer alike (the wave-per-sample forward saves only the layers' input rows, which only the wave-per-sample backward
+  // can start from). Reads cfg, the pack offsets and the diagnostic switches — per call, nothing is kept: tests switch them
+  // between two passes of one process. whole_pass = false: a forward over another net's encoder output, or over one stage
+  // only, stays off the vision / option routes (as under V4L_NO_WPS_LAYERS).
+  v4l::LayerRoute layer_route(bool whole_pass = true) const;
+  bool wps_tail_shape() const;  // the proprio MLP the wave-per-sample backward continues into (256-256)
   // round 4: the pooled heads' data-grads ran beside the loss statistics (heads_ext() handed the trainer their operands) for
   // the backward pass over (heads_ext_ws, heads_ext_n) that follows; backward_t consumes the mark
   float* heads_ext_ws = nullptr;
   int heads_ext_n = 0;
-  bool wps_bwd_plain() const;   // backward_t will run the (non-vision) wave-per-sample backward
-  int heads_ext(float* ws, int n, v4l::RowsChain* out);
+  int heads_ext(float* ws, int n, v4l::RowsChain* out, bool critic = false);
   // round 6: the trainer handed over the loss of the pass (rows, scalars, where the statistics go) — backward_t then runs the
   // layers' forward, the loss rows and the backward as ONE launch (csrc/wps_fb.h) over a workspace whose forward stopped behind
-  // the encoder (forward_t stage 1); backward_t consumes the mark
+  // the encoder (forward_t stage 1); backward_t consumes the mark. Only for a net whose layer_route().fb_allowed says so.
   const v4l::FbLoss* fb_loss = nullptr;
-  bool fb_ok() const;         // ... which serves the plain shipped LocoTransformer
-  bool fused_layers() const;  // the transformer layers run as fused forward / backward launches (csrc/infer.h, bwd.h)
-  bool wps_layers() const;
-  bool wps_max_pool() const;  // max_pool=True pooled inside the wave-per-sample pair
-  bool wps_opt() const;       // token_norm / use_pytorch_encoder / another proprio MLP around the wave-per-sample layers
-  bool wps_opt_vis() const;   // the same for the vision-only Transformer (native 16-token kernels, 17-row slots)
-  bool wps_tail_shape() const;  // the proprio MLP the wave-per-sample backward continues into (256-256)
-  bool wps_vis() const;  // vision-only Transformer on the wave-per-sample kernels (dummy token row, csrc/wps.h)    // ... as wave-per-sample launches (csrc/wps.h)
   template <typename T> int backward_t(const float* state, const T* image, const int* rowidx, int n, float* ws, float* grads, hipStream_t s);
 };
 

@@ -216,6 +216,7 @@ struct Ctx {  // per-call view of a bound net
   bool fb_pending = false;
   v4l::FbLoss fb_args = {};
   int fb_blocks = 0, fb_n = 0;
+  bool taps = false;  // LayerRoute::taps of the pass: bwd_conv_kernel writes dc2 / dc1 out too
 };
 
 // Fork/join of the net's auxiliary stream. Independent sibling kernels (a layer's weight-grad next to its data-grad,
@@ -657,7 +658,7 @@ static int conv_stack_bwd_fused(Ctx& c, const T* image, const int* rowidx, int n
   a.w3d = (const T*)N->packed + N->conv[2].pkd[0];
   for (int cls = 0; cls < 4; ++cls) a.w2d[cls] = (const T*)N->packed + N->conv[1].pkd[cls];
   a.image = image; a.rowidx = rowidx; a.c1 = c1; a.c2 = c2; a.dc3 = dc3;
-  if (sw_on("V4L_LAYER_TAPS")) { a.t_dc2 = dc2_tap; a.t_dc1 = dc1_tap; }  // (tests; read per call)
+  if (c.taps) { a.t_dc2 = dc2_tap; a.t_dc1 = dc1_tap; }  // (tests)
   a.slab1 = slab[0]; a.slab2 = slab[1]; a.slab3 = slab[2];
   a.bslab1 = bslab[0]; a.bslab2 = bslab[1]; a.bslab3 = bslab[2];
   a.n = n;
@@ -1072,78 +1073,75 @@ static bool dense_stack_shape(const v4l_net* N) {
   return c.visual_dim == 256 && c.n_enc_hidden == 2 && c.enc_hidden[0] == 256 && c.enc_hidden[1] == 256 && N->proj.pkf >= 0 &&
          N->proj.pkft >= 0 && N->proj.Kp == 1024 && N->enc[1].pkft >= 0 && N->head[0].Kp == 512;
 }
-bool v4l_net::wps_layers() const {
-  return fused_layers() && cfg.n_layers == 2 && layers[0].inproj.pkp >= 0 && !sw_on("V4L_NO_WPS_LAYERS");
+// the shapes the fused kernels are specialised for: the proprio MLP 256-256 on at most 128 inputs, heads 256-256, 4 x 64 x 64 depth
+static bool mlp_256(const v4l_net_cfg& c) {
+  return c.n_enc_hidden == 2 && c.enc_hidden[0] == 256 && c.enc_hidden[1] == 256 && c.state_dim <= 128;
 }
-// V4L_VIS17=1 (read per call: a test switches it): the vision-only Transformer on the 17-row wave-per-sample instantiation (dummy
-// row 0) instead of the native 16-token one — the two are cross-checked against each other
-static bool vis17_forced() { return sw_on("V4L_VIS17"); }
-bool v4l_net::wps_vis() const {
-  const v4l_net_cfg& c = cfg;
-  return c.kind == V4L_NET_LOCO_VIS && !c.token_norm && !c.pytorch_encoder && c.ff_dim == 256 && c.n_layers == 2 && c.n_head_hidden == 2 && c.head_hidden[0] == 256 &&
-         c.head_hidden[1] == 256 && c.out_dim <= OUT_LD && layers[0].inproj.pkp >= 0 && head[0].pko >= 0 &&
-         !sw_on("V4L_NO_WPS_LAYERS");
-}
-// max_pool=True on the (non-vision) wave-per-sample pair: forward and backward must both take it (the block-cooperative kernels
-// pool by mean only)
-bool v4l_net::wps_max_pool() const {
-  const v4l_net_cfg& c = cfg;
-  return c.kind == V4L_NET_LOCO && c.n_layers == 2 && c.n_enc_hidden == 2 && c.enc_hidden[0] == 256 && c.enc_hidden[1] == 256 &&
-         !sw_on("V4L_NO_LAYER_STACK") && wps_layers();
-}
-// The wave-per-sample layers with layer-by-layer launches around them (round 5): token_norm / use_pytorch_encoder, or a proprio MLP
-// that is not the shipped 256-256 one. The LocoTransformer's two layers (and, without the final LayerNorm, its pooled heads) run
-// on the wave-per-sample kernels; token_ln, the final norm with the pooling and heads behind it, and (token_norm, other proprio
-// MLPs) the encoder-side data-grads stay separate launches of the layer-by-layer path. Forward and backward decide alike.
-bool v4l_net::wps_tail_shape() const {
+static bool head_256(const v4l_net_cfg& c) { return c.n_head_hidden == 2 && c.head_hidden[0] == 256 && c.head_hidden[1] == 256; }
+static bool depth_64(const v4l_net_cfg& c) { return c.in_channels == 4 && c.img_hw == 64; }
+bool v4l_net::wps_tail_shape() const {  // (mlp_256 without its bound on state_dim, which belongs to the encoder kernels)
   return cfg.n_enc_hidden == 2 && cfg.enc_hidden[0] == 256 && cfg.enc_hidden[1] == 256;
 }
-bool v4l_net::wps_opt() const {
+// The route of the Transformer layers (net.h LayerRoute). The wave-per-sample kernels (csrc/wps.h) serve two layers of ff_dim 256
+// under 256-256 heads; what surrounds the layers picks the family. Everything else with ff_dim 256 and neither token_norm nor
+// use_pytorch_encoder runs the block-cooperative kernels (csrc/infer.h, bwd.h), the rest layer by layer.
+LayerRoute v4l_net::layer_route(bool whole_pass) const {
   const v4l_net_cfg& c = cfg;
-  if (c.kind != V4L_NET_LOCO || c.max_pool) return false;
-  if (!(c.token_norm || c.pytorch_encoder) && wps_tail_shape()) return false;  // (the plain shipped net: wps_bwd_plain's launch)
-  return c.ff_dim == 256 && c.n_layers == 2 && c.n_head_hidden == 2 && c.head_hidden[0] == 256 && c.head_hidden[1] == 256 &&
-         c.out_dim <= OUT_LD && layers[0].inproj.pkp >= 0 && !sw_on("V4L_NO_WPS_LAYERS") &&
-         !sw_on("V4L_NO_LAYER_STACK") && !sw_on("V4L_LAYER_TAPS");
-}
-// The same for the vision-only Transformer: its layers on the native 16-token wave-per-sample kernels (17-row slots, tokens in
-// rows 1..16) with token_ln / the final norm + pooling + heads as launches over the 17-row slots (the dummy rows zeroed).
-bool v4l_net::wps_opt_vis() const {
-  const v4l_net_cfg& c = cfg;
-  if (c.kind != V4L_NET_LOCO_VIS || !(c.token_norm || c.pytorch_encoder) || c.max_pool) return false;
-  return c.ff_dim == 256 && c.n_layers == 2 && c.n_head_hidden == 2 && c.head_hidden[0] == 256 && c.head_hidden[1] == 256 &&
-         c.out_dim <= OUT_LD && layers[0].inproj.pkp >= 0 && head[0].pko >= 0 && !sw_on("V4L_NO_WPS_LAYERS") &&
-         !sw_on("V4L_NO_LAYER_STACK") && !sw_on("V4L_LAYER_TAPS");
-}
-bool v4l_net::fused_layers() const {
-  return cfg.kind == V4L_NET_LOCO && cfg.ff_dim == 256 && !cfg.token_norm && !cfg.pytorch_encoder;
-}
-// backward_t's own conditions for the (non-vision) wave-per-sample backward, for callers that prepare work for it
-bool v4l_net::wps_bwd_plain() const {
-  const v4l_net_cfg& c = cfg;
-  if (c.kind != V4L_NET_LOCO) return false;
-  const bool fused_bwd = fused_layers();
-  const bool fused_head = fused_bwd && c.n_layers >= 1 && c.n_head_hidden == 2 && c.head_hidden[0] == 256 &&
-                          c.head_hidden[1] == 256 && c.out_dim <= OUT_LD && (!c.max_pool || wps_max_pool());
-  const bool fused_tail = fused_bwd && c.n_layers >= 1 && c.n_enc_hidden == 2 && c.enc_hidden[0] == 256 &&
-                          c.enc_hidden[1] == 256;
-  return fused_bwd && fused_head && fused_tail && c.n_layers == 2 && !sw_on("V4L_NO_LAYER_STACK") && wps_layers();
-}
-// The fused forward-loss-backward launch of the layers + heads (csrc/wps_fb.h) serves the plain shipped LocoTransformer on the
-// wave-per-sample kernels, mean pooling, no test taps. V4L_NO_FB (read per call: the cross-check tests switch it): the three
-// separate launches.
-bool v4l_net::fb_ok() const {
-  return wps_bwd_plain() && !cfg.max_pool && !sw_on("V4L_LAYER_TAPS") && !sw_on("V4L_NO_FB") && !sw_on("V4L_WPS_HEAD_IN") &&
-         !sw_on("V4L_WPS_HEAD_EXT_CRITIC");
+  LayerRoute r;
+  // (read per call: tests switch them)
+  r.taps = sw_on("V4L_LAYER_TAPS");
+  r.stack_ok = !sw_on("V4L_NO_LAYER_STACK");
+  r.tok0_in = sw_on("V4L_WPS_TOK0_IN");
+  r.par_wgrad = sw_int("V4L_PAR_WGRAD", 2);
+  const bool no_wps = sw_on("V4L_NO_WPS_LAYERS"), vis17 = sw_on("V4L_VIS17"), no_fb = sw_on("V4L_NO_FB");
+  const bool head_in = sw_on("V4L_WPS_HEAD_IN"), ext_critic = sw_on("V4L_WPS_HEAD_EXT_CRITIC");
+  if (!is_tf()) return r;
+  const bool vis = c.kind == V4L_NET_LOCO_VIS, opt = c.token_norm || c.pytorch_encoder;
+  const bool heads = head_256(c) && c.out_dim <= OUT_LD;
+  const bool wps = c.ff_dim == 256 && c.n_layers == 2 && heads && layers[0].inproj.pkp >= 0 && !no_wps &&
+                   (!vis || head[0].pko >= 0);
+  // the routes with layer-by-layer launches around the wave-per-sample pair: mean pooling only, no test taps, a pass of their own
+  const bool around = wps && whole_pass && !c.max_pool && r.stack_ok && !r.taps;
+  r.family = LayerFamily::LAYER_BY_LAYER;
+  if (vis) {
+    // V4L_VIS17=1 (a test switches it) and the tapped test build: the 17-row instantiation (dummy row 0) instead of the native
+    // 16-token one — the two are cross-checked against each other
+    if (wps && whole_pass && !opt) r.family = (vis17 || r.taps) ? LayerFamily::WPS_VIS17 : LayerFamily::WPS_VIS;
+    else if (around && opt) r.family = LayerFamily::WPS_OPT_VIS;
+    r.rows17 = r.wps();
+    r.heads_in = r.wps() && !c.pytorch_encoder;
+    r.tail_in = r.wps() && !c.token_norm;
+    return r;
+  }
+  const bool plain = !opt && wps_tail_shape();  // the shipped net; max_pool=True pools inside the wave-per-sample pair only
+  if (wps && plain && r.stack_ok) {
+    r.family = LayerFamily::WPS_PLAIN;
+    r.heads_in = r.tail_in = true;
+    r.heads_ext_allowed = !head_in && !r.taps;
+    r.heads_ext_critic = r.heads_ext_allowed && ext_critic;
+    r.fb_allowed = r.heads_ext_allowed && !c.max_pool && !no_fb && !ext_critic;
+  } else if (around && !plain) {
+    // (use_pytorch_encoder alone leaves the encoder-side data-grads inside the launch like the plain net; token_norm takes them
+    // layer by layer from token_ln's backward, another proprio MLP from the layer-0 input gradient)
+    r.family = LayerFamily::WPS_OPT;
+    r.heads_in = !c.pytorch_encoder;
+    r.tail_in = !c.token_norm && wps_tail_shape();
+  } else if (c.ff_dim == 256 && !opt) {
+    // the last layer's blocks also run the pooled heads of their samples (mean pooling), layer 0's continue into the proprio MLP
+    r.heads_in = c.n_layers >= 1 && heads && !c.max_pool;
+    r.tail_in = c.n_layers >= 1 && wps_tail_shape();
+    r.family = (r.heads_in && c.n_layers == 2 && r.stack_ok) ? LayerFamily::BLOCK_STACK : LayerFamily::BLOCK_PER_LAYER;
+  }
+  return r;
 }
 // The operands of the pooled heads' data-grad chain over the workspace `ws` laid out for n rows, for a caller (the trainer's
 // loss launch) that runs the chain itself right before v4l_net_backward(ws, n): -> 1 and the backward pass is told (it then
 // starts from dpool), or 0 when that backward pass will not be the wave-per-sample one (or V4L_WPS_HEAD_IN / test taps ask for
 // the in-kernel heads).
-int v4l_net::heads_ext(float* ws, int n, v4l::RowsChain* out) {
+int v4l_net::heads_ext(float* ws, int n, v4l::RowsChain* out, bool critic) {
   heads_ext_ws = nullptr;
-  if (!bound || out == nullptr || !wps_bwd_plain() || sw_on("V4L_WPS_HEAD_IN") || sw_on("V4L_LAYER_TAPS"))
-    return 0;
+  const LayerRoute r = layer_route();
+  if (!bound || out == nullptr || !(critic ? r.heads_ext_critic : r.heads_ext_allowed)) return 0;
   const Layout L = layout(n);
   const size_t es = is_half(cfg.compute) ? 2 : 4;
   const char* base = (const char*)packed;
@@ -1261,6 +1259,37 @@ Layout v4l_net::layout(int n) const {
 }
 
 // ------------------------------------------------------------------------------------------ forward
+// The weights of one TransformerEncoderLayer / of the pooled heads as the fused layer kernels take them (csrc/infer.h). frag: the
+// k-permuted fragment-order packs of the wave-per-sample kernels (pkp), else the row-major packs of the block-cooperative ones.
+// The caller adds xout and the saves of its launch.
+template <typename T>
+static InfLayer inf_layer(const v4l_net* N, const TLayer& t, bool frag, const float* xin) {
+  const T* base = (const T*)N->packed;
+  float* const* p = N->p.data();
+  InfLayer d;
+  memset(&d, 0, sizeof(d));
+  d.win = base + (frag ? t.inproj.pkp : t.inproj.pk); d.wo = base + (frag ? t.outproj.pkp : t.outproj.pk);
+  d.w1 = base + (frag ? t.ff1.pkp : t.ff1.pk); d.w2 = base + (frag ? t.ff2.pkp : t.ff2.pk);
+  d.bin = p[t.inproj.b]; d.bo = p[t.outproj.b]; d.b1 = p[t.ff1.b]; d.b2 = p[t.ff2.b];
+  d.g1 = p[t.ln1.g]; d.be1 = p[t.ln1.b]; d.g2 = p[t.ln2.g]; d.be2 = p[t.ln2.b];
+  d.xin = xin;
+  return d;
+}
+// pko: the vision-only net's first head layer, whose 64 real K entries sit in the pooled operand's second half
+template <typename T>
+static InfHead inf_head(const v4l_net* N, const Layout& L, float* ws, bool pko) {
+  const T* base = (const T*)N->packed;
+  float* const* p = N->p.data();
+  const std::vector<Lin>& head = N->head;
+  InfHead h;
+  memset(&h, 0, sizeof(h));
+  h.w0 = base + (pko ? head[0].pko : head[0].pk); h.w1 = base + head[1].pk; h.w2 = base + head[2].pk;
+  h.b0 = p[head[0].b]; h.b1 = p[head[1].b]; h.b2 = p[head[2].b];
+  h.out = ws + L.out; h.nout = N->cfg.out_dim; h.max_pool = N->cfg.max_pool;  // (pooling by max: the wave-per-sample kernels only)
+  h.s_pooled = ws + L.pooled; h.s_h0 = ws + L.hh[0]; h.s_h1 = ws + L.hh[1];
+  return h;
+}
+
 template <typename T>
 int v4l_net::forward_t(const float* state, const T* image, const int* rowidx, int n, float* ws, hipStream_t s,
                        const float* enc_ws, int stage) {
@@ -1273,6 +1302,9 @@ int v4l_net::forward_t(const float* state, const T* image, const int* rowidx, in
   Act eacts[V4L_MAX_HIDDEN];
   for (int i = 0; i < ne; ++i) eacts[i] = Act{ws + L.eh[i], c.enc_hidden[i], c.enc_hidden[i]};
   ADense head_in;
+  // the Transformer layers' route (and the switches it read): a forward that starts from another net's encoder output, or runs
+  // one stage only, stays off the vision / option routes (their 17-row slots are laid out by the encoder pass of a whole forward)
+  const LayerRoute r = layer_route(enc_ws == nullptr && stage == 0);
   // an encoder pass over this workspace rewrites its c1 / c2: whatever type they held is gone (train_enc marks it again)
   if (enc_ws == nullptr && stage != 2 && c.kind != V4L_NET_MLP && acts16_c1 == ws + L.c1) acts16_c1 = nullptr;
   // persistent 16-wave encoder blocks (csrc/infer.h train_encoder_kernel<MODE>): conv weights enter a CU once, not once per
@@ -1301,7 +1333,7 @@ int v4l_net::forward_t(const float* state, const T* image, const int* rowidx, in
     te.s_h1 = prop ? ws + L.eh[0] : nullptr; te.s_h2 = s_h2; te.ld_h2 = ld_h2;
     te.n = n; te.nmlp = prop ? cdiv(n, 32) : 0;
     // (V4L_ACTS_F32: keep c1 / c2 in fp32 — the cross-check of tests/test_gpu_parity.py::test_conv_acts_in_operand_type_same_bits)
-    te.acts16 = want_acts16 && conv_bwd_fusable(this) && !sw_on("V4L_LAYER_TAPS") && !sw_on("V4L_ACTS_F32");
+    te.acts16 = want_acts16 && conv_bwd_fusable(this) && !r.taps && !sw_on("V4L_ACTS_F32");
     if (te.acts16) acts16_c1 = te.s_c1;
     constexpr int cus = 256;
     // the conv share never collapses: a very large minibatch (n >~ 8 K: nmlp -> cus) still gets half the CUs' worth of
@@ -1386,15 +1418,14 @@ int v4l_net::forward_t(const float* state, const T* image, const int* rowidx, in
     } else if (enc_ws == nullptr && stage != 2 && c.kind == V4L_NET_LOCO_VIS) {
       // TransformerEncoder (base.py:388-494, depth only): conv stack -> 1x1 up-conv -> the 16 patch tokens, in order
       // wave-per-sample path: the 16 tokens go to rows 1..16 of a 17-row stride (row 0 = the dummy row, csrc/wps.h)
-      const bool rows17 = stage == 0 && (wps_vis() || wps_opt_vis());
       if (train_enc_ok) {
-        if (rows17) rc = train_enc(std::integral_constant<int, ENC_TOK17>(), x0, nullptr, 0, false);
+        if (r.rows17) rc = train_enc(std::integral_constant<int, ENC_TOK17>(), x0, nullptr, 0, false);
         else rc = train_enc(std::integral_constant<int, ENC_TOK16>(), x0, nullptr, 0);
         if (rc) return rc;
       } else {
         if ((rc = conv_stack_fwd<T>(cx, image, rowidx, n, ws + L.c1, ws + L.c2, ws + L.c3))) return rc;
         Epi ep = mk_epi(x0, TD, TD);
-        if (rows17) ep.rowmap = ROWMAP_TOK_DEPTH;
+        if (r.rows17) ep.rowmap = ROWMAP_TOK_DEPTH;
         if ((rc = lin_fwd<T>(cx, upconv, dense(ws + L.c3, 64, n * 16, 64), ep))) return rc;
       }
     } else if (enc_ws == nullptr && stage != 2) {
@@ -1419,7 +1450,7 @@ int v4l_net::forward_t(const float* state, const T* image, const int* rowidx, in
     if (stage == 1) return 0;
     // (vision-only net with token_norm / use_pytorch_encoder on the wave-per-sample layers: 17-row slots, the dummy rows zeroed
     // wherever a LayerNorm launch walks over them)
-    const bool vis_opt = c.kind == V4L_NET_LOCO_VIS && wps_opt_vis() && enc_ws == nullptr && stage == 0;
+    const bool vis_opt = r.family == LayerFamily::WPS_OPT_VIS;
     const int R = n * (vis_opt ? NTOK : ntok);
     auto zero_row0 = [&](float* rows) {
       return hipMemset2DAsync(rows, (size_t)NTOK * TD * sizeof(float), 0, (size_t)TD * sizeof(float), (size_t)n, s);
@@ -1433,151 +1464,108 @@ int v4l_net::forward_t(const float* state, const T* image, const int* rowidx, in
       V4L_LAUNCH_CHECK();
       x0 = ws + L.x[0];
     }
-    const bool fused_layers = this->fused_layers();
-    // the last layer's blocks also run the pooled heads of their samples when the head stack has the shipped shape
-    // (max_pool=True pools inside the wave-per-sample kernels only: the block-cooperative fallback keeps pool_fwd_kernel)
-    const bool fused_head = fused_layers && c.n_layers >= 1 && nh == 2 && c.head_hidden[0] == 256 && c.head_hidden[1] == 256 &&
-                            c.out_dim <= OUT_LD && (!c.max_pool || wps_max_pool());
-    // both layers + the heads in ONE launch when the stack is the shipped two layers (the token rows stay in LDS between
-    // the layers); otherwise one launch per TransformerEncoderLayer. 2 or 4 samples per block, saving what backward_t reads.
-    const bool stack_ok = !sw_on("V4L_NO_LAYER_STACK");  // (read per call: tests switch it)
-    const bool stacked = fused_layers && fused_head && c.n_layers == 2 && stack_ok;
-    const bool vis_wps = c.kind == V4L_NET_LOCO_VIS && enc_ws == nullptr && stage == 0 && wps_vis();
-    // (wps_bwd_plain: the wave-per-sample forward keeps only the layers' input rows, which only the wave-per-sample backward
-    // can start from — a geometry whose backward stays layer-by-layer must not take it)
-    const bool opt_wps = (wps_opt() && enc_ws == nullptr && stage == 0) || vis_opt;
-    bool wps_layers_done = false;  // (use_pytorch_encoder on the wave-per-sample layers: norm, pooling and heads still to come)
-    if ((stacked && wps_layers() && wps_bwd_plain()) || vis_wps || opt_wps) {
+    InfHeadPair hd;  // (an option route without heads_in launches with the slots filled too; its kernel does not read them)
+    memset(&hd, 0, sizeof(hd));
+    if (r.wps() || r.heads_in) hd.n[0] = inf_head<T>(this, L, ws, r.rows17);
+    g_op = "layer";
+    if (r.wps()) {
       // wave-per-sample launch (csrc/wps.h): both layers + the pooled heads, 4 samples per block, weights resident in LDS
-      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, true, 2, false>>(WpsFwdLds<T>::bytes));
-      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, true, 2, true>>(WpsFwdLds<T>::bytes));
-      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, true, 2, false, true>>(WpsFwdLds<T>::bytes));
-      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, true, 2, true, true>>(WpsFwdLds<T>::bytes));
-      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, true, 2, false, 2>>(WpsFwdLds<T>::bytes));
-      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, false, 2, false>>(WpsFwdLds<T>::bytes));
-      V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, false, 2, false, 2>>(WpsFwdLds<T>::bytes));
-      const bool taps = sw_on("V4L_LAYER_TAPS");  // (read per call: tests switch it)
-      const T* base = (const T*)packed;
       InfLayerStack stk;
       memset(&stk, 0, sizeof(stk));
       stk.nl = 2;
       for (int k = 0; k < 2; ++k) {
-        const TLayer& t = layers[k];
         const LayerWs& w = L.lw[k];
         InfLayer& d = stk.l[k].n[0];
-        d.win = base + t.inproj.pkp; d.wo = base + t.outproj.pkp; d.w1 = base + t.ff1.pkp; d.w2 = base + t.ff2.pkp;
-        d.bin = p[t.inproj.b]; d.bo = p[t.outproj.b]; d.b1 = p[t.ff1.b]; d.b2 = p[t.ff2.b];
-        d.g1 = p[t.ln1.g]; d.be1 = p[t.ln1.b]; d.g2 = p[t.ln2.g]; d.be2 = p[t.ln2.b];
-        d.xin = k == 0 ? x0 : ws + L.x[k];
+        d = inf_layer<T>(this, layers[k], true, k == 0 ? x0 : ws + L.x[k]);
         // production: the forward saves nothing but the layers' input rows (the backward recomputes, csrc/wps.h);
         // V4L_LAYER_TAPS=1 (tests): every intermediate goes out row-major, as the block-cooperative kernels save them
         // (max_pool: the backward finds the arg-max tokens again from the stack's output rows)
         // (use_pytorch_encoder: the final norm is a launch of its own behind this one)
-        d.xout = (k + 1 < 2 || taps || c.max_pool || c.pytorch_encoder) ? ws + L.x[k + 1] : nullptr;
-        if (taps) {
+        d.xout = (k + 1 < 2 || r.taps || c.max_pool || c.pytorch_encoder) ? ws + L.x[k + 1] : nullptr;
+        if (r.taps) {
           d.s_qkv = ws + w.qkv; d.s_P = ws + w.P; d.s_ctx = ws + w.ctx; d.s_xh1 = ws + w.xh1; d.s_rs1 = ws + w.rs1;
           d.s_x1 = ws + w.x1; d.s_f = ws + w.f; d.s_xh2 = ws + w.xh2; d.s_rs2 = ws + w.rs2;
           d.s_xin = sizeof(T) == 2 ? ws + w.xin : nullptr;
         }
       }
-      InfHeadPair hd;
-      memset(&hd, 0, sizeof(hd));
-      InfHead& h = hd.n[0];
-      h.w0 = base + ((vis_wps || vis_opt) ? head[0].pko : head[0].pk); h.w1 = base + head[1].pk; h.w2 = base + head[2].pk;
-      h.b0 = p[head[0].b]; h.b1 = p[head[1].b]; h.b2 = p[head[2].b];
-      h.out = ws + L.out; h.nout = c.out_dim; h.max_pool = c.max_pool;
-      h.s_pooled = ws + L.pooled; h.s_h0 = ws + L.hh[0]; h.s_h1 = ws + L.hh[1];
-      g_op = "layer";
-      if (vis_opt && c.pytorch_encoder)  // layers only: final norm, pooling and heads follow below
-        V4L_KLAUNCH("wps_layer_stack", 2.0 * n * (2 * 872576.0), s, (wps_layer_fwd_kernel<T, false, 2, false, 2>),
-                    dim3(cdiv(n, WPS_WPB)), dim3(256), (WpsFwdLds<T>::bytes), s, stk, hd, n);
-      else if (vis_opt)
-        V4L_KLAUNCH("wps_layer_stack_head", 2.0 * n * (2 * 872576.0 + 99840.0), s, (wps_layer_fwd_kernel<T, true, 2, false, 2>),
-                    dim3(cdiv(n, WPS_WPB)), dim3(256), (WpsFwdLds<T>::bytes), s, stk, hd, n);
-      else if (opt_wps && c.pytorch_encoder)
-        V4L_KLAUNCH("wps_layer_stack", 2.0 * n * (2 * 872576.0), s, (wps_layer_fwd_kernel<T, false, 2, false>),
-                    dim3(cdiv(n, WPS_WPB)), dim3(256), (WpsFwdLds<T>::bytes), s, stk, hd, n);
-      else if (vis_wps && taps)
-        V4L_KLAUNCH("wps_layer_stack_head", 2.0 * n * (2 * 872576.0 + 99840.0), s, (wps_layer_fwd_kernel<T, true, 2, true, true>),
-                    dim3(cdiv(n, WPS_WPB)), dim3(256), (WpsFwdLds<T>::bytes), s, stk, hd, n);
-      else if (vis_wps && vis17_forced())
-        V4L_KLAUNCH("wps_layer_stack_head", 2.0 * n * (2 * 872576.0 + 99840.0), s, (wps_layer_fwd_kernel<T, true, 2, false, true>),
-                    dim3(cdiv(n, WPS_WPB)), dim3(256), (WpsFwdLds<T>::bytes), s, stk, hd, n);
-      else if (vis_wps)  // native 16-token instantiation: one token tile per sample (round 5)
-        V4L_KLAUNCH("wps_layer_stack_head", 2.0 * n * (2 * 872576.0 + 99840.0), s, (wps_layer_fwd_kernel<T, true, 2, false, 2>),
-                    dim3(cdiv(n, WPS_WPB)), dim3(256), (WpsFwdLds<T>::bytes), s, stk, hd, n);
-      else if (taps)
-        V4L_KLAUNCH("wps_layer_stack_head", 2.0 * n * (2 * 872576.0 + 99840.0), s, (wps_layer_fwd_kernel<T, true, 2, true>),
-                    dim3(cdiv(n, WPS_WPB)), dim3(256), (WpsFwdLds<T>::bytes), s, stk, hd, n);
-      else
-        V4L_KLAUNCH("wps_layer_stack_head", 2.0 * n * (2 * 872576.0 + 99840.0), s, (wps_layer_fwd_kernel<T, true, 2, false>),
-                    dim3(cdiv(n, WPS_WPB)), dim3(256), (WpsFwdLds<T>::bytes), s, stk, hd, n);
-      V4L_LAUNCH_CHECK();
-      if (!(opt_wps && c.pytorch_encoder)) return 0;
-      wps_layers_done = true;
-    }
-    for (int l = 0; l < c.n_layers && fused_layers; l += stacked ? 2 : 1) {
-      static int spw = 2;  // samples per block: 2 (48 MFMA rows, 2 blocks/CU: measured 20 % faster) or 4 (80 rows, 1 block/CU)
-      constexpr bool spw4_fits = InfLayLds<T, 4>::bytes <= 160 * 1024;  // (not in the fp32 parity mode: 168 KB)
-      if (spw4_fits) {
-        V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, 4, false, 1>>(InfLayLds<T, 4>::bytes));
-        V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, 4, true, 1>>(InfLayLds<T, 4>::bytes));
-        V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, 4, true, 2>>(InfLayLds<T, 4>::bytes));
+#define V4L_WPS_FWD(HEAD_, TAPS_, VIS_)                                                                                   \
+  do {                                                                                                                    \
+    V4L_HIP_CHECK(lds_limit<&wps_layer_fwd_kernel<T, HEAD_, 2, TAPS_, VIS_>>(WpsFwdLds<T>::bytes));                       \
+    if (HEAD_)                                                                                                            \
+      V4L_KLAUNCH("wps_layer_stack_head", 2.0 * n * (2 * 872576.0 + 99840.0), s, (wps_layer_fwd_kernel<T, HEAD_, 2, TAPS_, VIS_>), \
+                  dim3(cdiv(n, WPS_WPB)), dim3(256), (WpsFwdLds<T>::bytes), s, stk, hd, n);                               \
+    else  /* layers only: final norm, pooling and heads follow below */                                                   \
+      V4L_KLAUNCH("wps_layer_stack", 2.0 * n * (2 * 872576.0), s, (wps_layer_fwd_kernel<T, HEAD_, 2, TAPS_, VIS_>),        \
+                  dim3(cdiv(n, WPS_WPB)), dim3(256), (WpsFwdLds<T>::bytes), s, stk, hd, n);                               \
+  } while (0)
+      switch (r.family) {
+        case LayerFamily::WPS_OPT_VIS:
+          if (r.heads_in) V4L_WPS_FWD(true, false, 2);
+          else V4L_WPS_FWD(false, false, 2);
+          break;
+        case LayerFamily::WPS_OPT:
+          if (r.heads_in) V4L_WPS_FWD(true, false, 0);
+          else V4L_WPS_FWD(false, false, 0);
+          break;
+        case LayerFamily::WPS_VIS17:
+          if (r.taps) V4L_WPS_FWD(true, true, 1);
+          else V4L_WPS_FWD(true, false, 1);
+          break;
+        case LayerFamily::WPS_VIS:  // native 16-token instantiation: one token tile per sample (round 5)
+          V4L_WPS_FWD(true, false, 2);
+          break;
+        default:  // WPS_PLAIN
+          if (r.taps) V4L_WPS_FWD(true, true, 0);
+          else V4L_WPS_FWD(true, false, 0);
       }
-      V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, 2, false, 1>>(InfLayLds<T, 2>::bytes));
-      V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, 2, true, 1>>(InfLayLds<T, 2>::bytes));
-      V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, 2, true, 2>>(InfLayLds<T, 2>::bytes));
-      const T* base = (const T*)packed;
+#undef V4L_WPS_FWD
+      V4L_LAUNCH_CHECK();
+    }
+    // block-cooperative kernels (csrc/infer.h): both layers + the heads in ONE launch when the stack is the shipped two layers
+    // (the token rows stay in LDS between the layers); otherwise one launch per TransformerEncoderLayer. 2 or 4 samples per
+    // block, saving what backward_t reads.
+    const bool stacked = r.family == LayerFamily::BLOCK_STACK;
+    for (int l = 0; l < c.n_layers && r.block(); l += stacked ? 2 : 1) {
+      // samples per block: 2 (48 MFMA rows, 2 blocks/CU: measured 20 % faster) or 4 (80 rows, 1 block/CU; not in fp32: 168 KB)
+      static int spw = 2;
       InfLayerStack stk;
       memset(&stk, 0, sizeof(stk));
       stk.nl = stacked ? 2 : 1;
       for (int k = 0; k < stk.nl; ++k) {
-        const TLayer& t = layers[l + k];
         const LayerWs& w = L.lw[l + k];
         InfLayer& d = stk.l[k].n[0];
-        d.win = base + t.inproj.pk; d.wo = base + t.outproj.pk; d.w1 = base + t.ff1.pk; d.w2 = base + t.ff2.pk;
-        d.bin = p[t.inproj.b]; d.bo = p[t.outproj.b]; d.b1 = p[t.ff1.b]; d.b2 = p[t.ff2.b];
-        d.g1 = p[t.ln1.g]; d.be1 = p[t.ln1.b]; d.g2 = p[t.ln2.g]; d.be2 = p[t.ln2.b];
-        d.xin = l + k == 0 ? x0 : ws + L.x[l + k];
+        d = inf_layer<T>(this, layers[l + k], false, l + k == 0 ? x0 : ws + L.x[l + k]);
         d.xout = ws + L.x[l + k + 1];
         d.s_qkv = ws + w.qkv; d.s_P = ws + w.P; d.s_ctx = ws + w.ctx; d.s_xh1 = ws + w.xh1; d.s_rs1 = ws + w.rs1;
         d.s_x1 = ws + w.x1; d.s_f = ws + w.f; d.s_xh2 = ws + w.xh2; d.s_rs2 = ws + w.rs2;
         d.s_xin = sizeof(T) == 2 ? ws + w.xin : nullptr;  // fp32 mode: the fp32 token tensor itself is the operand
       }
-      InfHeadPair hd;
-      memset(&hd, 0, sizeof(hd));
+      const bool head_on = r.heads_in && l + stk.nl == c.n_layers;  // the last layer's blocks run the heads of their samples
+      InfHeadPair none;
+      memset(&none, 0, sizeof(none));
+      const InfHeadPair& hp = head_on ? hd : none;
       InfFinish fin;
       memset(&fin, 0, sizeof(fin));
-      g_op = "layer";
-      if (fused_head && l + stk.nl == c.n_layers) {
-        InfHead& h = hd.n[0];
-        h.w0 = base + head[0].pk; h.w1 = base + head[1].pk; h.w2 = base + head[2].pk;
-        h.b0 = p[head[0].b]; h.b1 = p[head[1].b]; h.b2 = p[head[2].b];
-        h.out = ws + L.out; h.nout = c.out_dim;
-        h.s_pooled = ws + L.pooled; h.s_h0 = ws + L.hh[0]; h.s_h1 = ws + L.hh[1];
-        if (stacked && spw == 2)
-          V4L_KLAUNCH("fused_layer_stack_head", 2.0 * n * (2 * 872576.0 + 99840.0), s, (infer_layer_kernel<T, 2, true, 2>),
-                      dim3(cdiv(n, 2), 1), dim3(256), (InfLayLds<T, 2>::bytes), s, stk, hd, fin, n, c.ff_dim);
-        else if (stacked)
-          V4L_KLAUNCH("fused_layer_stack_head", 2.0 * n * (2 * 872576.0 + 99840.0), s, (infer_layer_kernel<T, 4, true, 2>),
-                      dim3(cdiv(n, 4), 1), dim3(256), (InfLayLds<T, 4>::bytes), s, stk, hd, fin, n, c.ff_dim);
-        else if (spw == 2)
-          V4L_KLAUNCH("fused_layer_head", 2.0 * n * (872576.0 + 99840.0), s, (infer_layer_kernel<T, 2, true, 1>), dim3(cdiv(n, 2), 1),
-                      dim3(256), (InfLayLds<T, 2>::bytes), s, stk, hd, fin, n, c.ff_dim);
-        else
-          V4L_KLAUNCH("fused_layer_head", 2.0 * n * (872576.0 + 99840.0), s, (infer_layer_kernel<T, 4, true, 1>), dim3(cdiv(n, 4), 1),
-                      dim3(256), (InfLayLds<T, 4>::bytes), s, stk, hd, fin, n, c.ff_dim);
-      } else if (spw == 2) {
-        V4L_KLAUNCH("fused_layer", 2.0 * n * 872576.0, s, (infer_layer_kernel<T, 2, false, 1>), dim3(cdiv(n, 2), 1), dim3(256),
-                    (InfLayLds<T, 2>::bytes), s, stk, hd, fin, n, c.ff_dim);
-      } else {
-        V4L_KLAUNCH("fused_layer", 2.0 * n * 872576.0, s, (infer_layer_kernel<T, 4, false, 1>), dim3(cdiv(n, 4), 1), dim3(256),
-                    (InfLayLds<T, 4>::bytes), s, stk, hd, fin, n, c.ff_dim);
-      }
+#define V4L_BLOCK_FWD(SPW_, HEAD_, NL_, LABEL_, FLOPS_)                                                                   \
+  do {                                                                                                                    \
+    V4L_HIP_CHECK(lds_limit<&infer_layer_kernel<T, SPW_, HEAD_, NL_>>(InfLayLds<T, SPW_>::bytes));                        \
+    V4L_KLAUNCH(LABEL_, FLOPS_, s, (infer_layer_kernel<T, SPW_, HEAD_, NL_>), dim3(cdiv(n, SPW_), 1), dim3(256),          \
+                (InfLayLds<T, SPW_>::bytes), s, stk, hp, fin, n, c.ff_dim);                                               \
+  } while (0)
+#define V4L_BLOCK_FWDS(SPW_)                                                                                              \
+  do {                                                                                                                    \
+    if (stacked) V4L_BLOCK_FWD(SPW_, true, 2, "fused_layer_stack_head", 2.0 * n * (2 * 872576.0 + 99840.0));              \
+    else if (head_on) V4L_BLOCK_FWD(SPW_, true, 1, "fused_layer_head", 2.0 * n * (872576.0 + 99840.0));                   \
+    else V4L_BLOCK_FWD(SPW_, false, 1, "fused_layer", 2.0 * n * 872576.0);                                                \
+  } while (0)
+      if (spw == 2) V4L_BLOCK_FWDS(2);
+      else V4L_BLOCK_FWDS(4);
+#undef V4L_BLOCK_FWDS
+#undef V4L_BLOCK_FWD
       V4L_LAUNCH_CHECK();
     }
-    if (fused_head) return 0;
-    for (int l = 0; l < c.n_layers && !fused_layers && !wps_layers_done; ++l) {
+    if (r.heads_in) return 0;
+    for (int l = 0; l < c.n_layers && r.family == LayerFamily::LAYER_BY_LAYER; ++l) {
       const TLayer& t = layers[l];
       const LayerWs& w = L.lw[l];
       float* xin = l == 0 ? x0 : ws + L.x[l];
@@ -1658,6 +1646,8 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
   const Layout L = layout(n);
   const v4l_net_cfg& c = cfg;
   Ctx cx{this, s, grads, ws + L.slab, 0, s};
+  const LayerRoute r = layer_route();  // the Transformer layers' route, as the forward of this pass took it, and the switches
+  cx.taps = r.taps;
   red.clear();
   tnp.clear();
   tnp_flops = 0;
@@ -1692,7 +1682,7 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
   // data-grads 33.7 (bwd_conv_kernel holds every CU: nothing fits beside it); conv-stack data-grads FIRST, then dW3 on the
   // main stream next to the two dense launches on the auxiliary stream 32.8 (default); three branches 34.8.
   // V4L_PAR_WGRAD=0: serial, 1: the older fork.
-  const int par_wgrad = sw_int("V4L_PAR_WGRAD", 2);  // (read per call: tests switch it)
+  const int par_wgrad = r.par_wgrad;
   if (par_wgrad == 2 || par_wgrad == 3) {
     cx.defer_conv3 = true;
     if ((rc = conv_stack_bwd<T>(cx, image, rowidx, n, ws + L.c1, ws + L.c2, ws + L.dc3, ws + L.dc2, ws + L.dc1))) return rc;
@@ -1828,26 +1818,17 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
   const bool vis = c.kind == V4L_NET_LOCO_VIS;
   const int pw = vis ? TD : 2 * TD;  // pooled width
   // (vision-only net with token_norm / use_pytorch_encoder around the wave-per-sample layers: 17-row slots — see forward_t)
-  const bool vis_opt = vis && wps_opt_vis();
+  const bool vis_opt = r.family == LayerFamily::WPS_OPT_VIS;
   const int R = n * (vis_opt ? NTOK : ntok);
   auto zero_row0 = [&](float* rows) {
     return hipMemset2DAsync(rows, (size_t)NTOK * TD * sizeof(float), 0, (size_t)TD * sizeof(float), (size_t)n, s);
   };
-  const bool fused_bwd = fused_layers();  // forward and backward switch together: they share the T-typed saves
-  // the last layer's launch starts from dout (heads + un-pool), layer 0's launch continues into the encoder MLP / up-conv
-  const bool fused_head = fused_bwd && c.n_layers >= 1 && nh == 2 && c.head_hidden[0] == 256 && c.head_hidden[1] == 256 &&
-                          c.out_dim <= OUT_LD && (!c.max_pool || wps_max_pool());
-  const bool fused_tail = fused_bwd && c.n_layers >= 1 && ne == 2 && c.enc_hidden[0] == 256 && c.enc_hidden[1] == 256;
-  // vision-only Transformer on the wave-per-sample kernels (17-row stride, dummy row 0: csrc/wps.h); the forward took the same path
-  const bool vis_wps = vis && wps_vis();
-  // token_norm / use_pytorch_encoder around the wave-per-sample layers (wps_opt): without the final norm the heads run inside
-  // the layers' launch as usual; with it they (and the pooling and the norm) are the layer-by-layer launches below
-  const bool opt_wps = wps_opt() || vis_opt;
-  const bool opt_heads_in = opt_wps && !c.pytorch_encoder;
-  if (fused_head || vis_wps || opt_heads_in) {  // only the three weight-grads are registered here
+  // heads_in: the last layer's launch starts from dout (heads + un-pool); tail_in: layer 0's continues into the encoder MLP /
+  // up-conv. (An option route with the final norm: it, the pooling and the heads are the layer-by-layer launches below.)
+  if (r.heads_in) {  // only the three weight-grads are registered here
     if ((rc = lin_wgrad<T>(cx, head[2], dy, dense(hacts[1].p, 256, n, 256), 256))) return rc;
     if ((rc = lin_wgrad<T>(cx, head[1], dense(dhhp[1], 256, n, 256), dense(hacts[0].p, 256, n, 256), 256))) return rc;
-    if (vis_wps || vis_opt) rc = lin_wgrad<T>(cx, head[0], dense(dhhp[0], 256, n, 256), dense(ws + L.pooled + TD, 2 * TD, n, TD), TD);
+    if (r.rows17) rc = lin_wgrad<T>(cx, head[0], dense(dhhp[0], 256, n, 256), dense(ws + L.pooled + TD, 2 * TD, n, TD), TD);
     else rc = lin_wgrad<T>(cx, head[0], dense(dhhp[0], 256, n, 256), dense(ws + L.pooled, 2 * TD, n, 2 * TD), 2 * TD);
     if (rc) return rc;
   } else {
@@ -1871,25 +1852,34 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
     }
   }
   const int lnb = std::min(cdiv(R, 16), 128);
+  // the fused layer kernels leave dgamma / dbeta of a layer's two norms as per-block partials: gp2 | bp2 | gp1 | bp1, [nblk][64] each
+  auto reduce_ln_partials = [&](const TLayer& t, const float* part, int nblk) {
+    const int lnp[4] = {t.ln2.g, t.ln2.b, t.ln1.g, t.ln1.b};
+    for (int q = 0; q < 4; ++q) {
+      RedDesc o;
+      memset(&o, 0, sizeof(o));
+      o.slab = part + (int64_t)q * nblk * TD;
+      o.dW = grads + params[lnp[q]].goff;
+      o.nsplit = nblk; o.N = 1; o.K = TD; o.Npad = 1; o.Kpad = TD; o.Ktorch = TD;
+      red.push_back(o);
+    }
+  };
   // both layers (+ heads before, + encoder-side data-grads after) in ONE launch when the stack is the shipped two layers: the
   // upper layer's dx stays in LDS as the lower layer's dy; otherwise one launch per TransformerEncoderLayer (csrc/bwd.h).
   // Every data-grad of a layer has its intermediates in LDS; the four weight-grads are deferred to the grouped launch.
-  const bool bwd_stack_ok = !sw_on("V4L_NO_LAYER_STACK");
-  const bool stacked = fused_bwd && fused_head && fused_tail && c.n_layers == 2 && bwd_stack_ok;
-  const bool wps = (stacked && wps_layers()) || vis_wps || opt_wps;
-  if (wps) {
+  const bool stacked = r.family == LayerFamily::BLOCK_STACK && r.tail_in;
+  if (r.wps()) {
     // wave-per-sample launch (csrc/wps.h): heads -> per layer {recompute, backward} -> encoder-side data-grads; the four
     // weight-grads of each layer come from the fragment-order operand blocks it leaves, in one launch of their own
-    const bool taps = sw_on("V4L_LAYER_TAPS");  // (read per call: tests switch it)
+    const bool taps = r.taps, plain = r.family == LayerFamily::WPS_PLAIN;
     // round 4: the heads' and the proprio branch's data-grad chains outside this launch, 64 rows per block (csrc/wps.h
     // rows_chain): the heads ran beside the loss statistics when the trainer said so (heads_ext), the proprio chain rides in
     // the layers' weight-grad launch unless the grouped weight-grads (its consumer) go to a stream of their own
-    const bool head_ext = !vis_wps && !taps && !opt_wps && heads_ext_ws == ws && heads_ext_n == n;
+    const bool head_ext = plain && !taps && heads_ext_ws == ws && heads_ext_n == n;
     heads_ext_ws = nullptr;
-    const int par_wgrad_now = sw_int("V4L_PAR_WGRAD", 2);
     // (the option variants keep the proprio chain where the layer-0 gradient is: in the launch, or — token_norm — layer by layer
     // behind token_ln's backward)
-    const bool tok0_ext = !vis_wps && !taps && !opt_wps && par_wgrad_now != 3 && !sw_on("V4L_WPS_TOK0_IN");
+    const bool tok0_ext = plain && !taps && r.par_wgrad != 3 && !r.tok0_in;
     const int nblk = cdiv(n, WPS_WPB);
     const T* base = (const T*)packed;
     WpsBwdStack d;
@@ -1910,19 +1900,11 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
       e.gp2 = part; e.bp2 = part + (int64_t)nblk * TD; e.gp1 = part + 2 * (int64_t)nblk * TD; e.bp1 = part + 3 * (int64_t)nblk * TD;
       e.o_dx = (li == 0 || taps) ? ws + L.dxl[li] : nullptr;  // layer 0's: operand of the projector / up-conv weight-grads
       if (taps) { e.t_dz2 = ws + b.dz2; e.t_df = ws + b.df; e.t_dz1 = ws + b.dz1; e.t_dqkv = ws + b.dqkv; }
-      const int lnp[4] = {t.ln2.g, t.ln2.b, t.ln1.g, t.ln1.b};
-      for (int q = 0; q < 4; ++q) {
-        RedDesc r;
-        memset(&r, 0, sizeof(r));
-        r.slab = part + (int64_t)q * nblk * TD;
-        r.dW = grads + params[lnp[q]].goff;
-        r.nsplit = nblk; r.N = 1; r.K = TD; r.Npad = 1; r.Kpad = TD; r.Ktorch = TD;
-        red.push_back(r);
-      }
+      reduce_ln_partials(t, part, nblk);
     }
     BwdHead bh;
     memset(&bh, 0, sizeof(bh));
-    bh.w2t = base + head[2].pkt; bh.w1t = base + head[1].pkt; bh.w0t = base + ((vis_wps || vis_opt) ? head[0].pkto : head[0].pkt);
+    bh.w2t = base + head[2].pkt; bh.w1t = base + head[1].pkt; bh.w0t = base + (r.rows17 ? head[0].pkto : head[0].pkt);
     bh.dout = ws + L.dout; bh.s_h1 = hacts[1].p; bh.s_h0 = hacts[0].p; bh.o_dh1 = dhhp[1]; bh.o_dh0 = dhhp[0];
     BwdTail bt;
     memset(&bt, 0, sizeof(bt));
@@ -1936,7 +1918,7 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
     tx.wupt_f = base + upconv.pkpt;
     tx.dpool = ws + L.dpool;
     tx.xlast = c.max_pool ? ws + L.x[c.n_layers] : nullptr;
-    tx.dyrows = (opt_wps && c.pytorch_encoder) ? ws + L.dxl[c.n_layers] : nullptr;  // (what the final norm's backward wrote)
+    tx.dyrows = !r.heads_in ? ws + L.dxl[c.n_layers] : nullptr;  // (what the final norm's backward wrote)
     g_op = "layer";
     const double fl_heads = 2.0 * n * 2 * (16 * 256 + 256 * 256 + 256 * 128) / 2, fl_tok0 = 2.0 * n * (64 * 256 + 256 * 256);
     const double fl = 2 * 4.0 * n * 872576.0 + (head_ext ? 0.0 : 2 * fl_heads) + (tok0_ext ? 0.0 : fl_tok0) + 2.0 * n * 16 * 64 * 64;
@@ -1949,28 +1931,19 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
     // round 6: forward -> loss rows -> backward as ONE launch when the trainer handed the loss over (csrc/wps_fb.h)
     const FbLoss* fbl = fb_loss;
     fb_loss = nullptr;
-    V4L_REQUIRE(fbl == nullptr || (fb_ok() && !vis_wps && !opt_wps && !taps && !head_ext),
+    V4L_REQUIRE(fbl == nullptr || (r.fb_allowed && !head_ext),
                 "internal: a fused forward-loss-backward pass was prepared for a net that does not take it");
-    const bool opt_notail = opt_wps && (c.token_norm || !(vis || wps_tail_shape()));
+    // MODE of the option routes: 1 = ends with the layer-0 input gradient rows, 2 = starts from the final norm's gradient rows, 3 = both
+    const bool m_out = r.opt() && !r.tail_in, m_in = r.opt() && !r.heads_in;
     if (fbl != nullptr) {
       InfLayerStack fst;
       memset(&fst, 0, sizeof(fst));
       fst.nl = 2;
-      for (int k = 0; k < 2; ++k) {
-        const TLayer& t = layers[k];
-        InfLayer& f = fst.l[k].n[0];
-        f.win = base + t.inproj.pkp; f.wo = base + t.outproj.pkp; f.w1 = base + t.ff1.pkp; f.w2 = base + t.ff2.pkp;
-        f.bin = p[t.inproj.b]; f.bo = p[t.outproj.b]; f.b1 = p[t.ff1.b]; f.b2 = p[t.ff2.b];
-        f.g1 = p[t.ln1.g]; f.be1 = p[t.ln1.b]; f.g2 = p[t.ln2.g]; f.be2 = p[t.ln2.b];
-        f.xin = k == 0 ? ws + L.x[0] : nullptr;  // (layer 1's input rows stay in the wave's registers)
-      }
+      for (int k = 0; k < 2; ++k)  // (layer 1's input rows stay in the wave's registers)
+        fst.l[k].n[0] = inf_layer<T>(this, layers[k], true, k == 0 ? ws + L.x[0] : nullptr);
       InfHeadPair fhd;
       memset(&fhd, 0, sizeof(fhd));
-      InfHead& h = fhd.n[0];
-      h.w0 = base + head[0].pk; h.w1 = base + head[1].pk; h.w2 = base + head[2].pk;
-      h.b0 = p[head[0].b]; h.b1 = p[head[1].b]; h.b2 = p[head[2].b];
-      h.out = ws + L.out; h.nout = c.out_dim;
-      h.s_pooled = ws + L.pooled; h.s_h0 = ws + L.hh[0]; h.s_h1 = ws + L.hh[1];
+      fhd.n[0] = inf_head<T>(this, L, ws, false);
       FbLoss lo = *fbl;
       lo.dout = ws + L.dout;
       cx.slab_used = (cx.slab_used + 1) & ~(int64_t)1;  // doubles
@@ -1992,20 +1965,31 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
       cx.fb_blocks = nblk;
       cx.fb_n = n;
     } else
-    if (vis_opt && opt_notail && c.pytorch_encoder) V4L_WPS_BWD(false, 2, true, true, 3);
-    else if (vis_opt && c.pytorch_encoder) V4L_WPS_BWD(false, 2, true, true, 2);
-    else if (vis_opt) V4L_WPS_BWD(false, 2, true, true, 1);
-    else if (opt_notail && c.pytorch_encoder) V4L_WPS_BWD(false, false, true, true, 3);
-    else if (opt_wps && c.pytorch_encoder) V4L_WPS_BWD(false, false, true, true, 2);  // from the final norm's gradient rows
-    else if (opt_wps) V4L_WPS_BWD(false, false, true, true, 1);                       // up to the layer-0 input gradient
-    else if (vis_wps && taps) V4L_WPS_BWD(true, true, true, true, 0);
-    else if (vis_wps && vis17_forced()) V4L_WPS_BWD(false, true, true, true, 0);
-    else if (vis_wps) V4L_WPS_BWD(false, 2, true, true, 0);  // native 16 tokens: no 17th-token side blocks (wa.l[].tk = null below)
-    else if (taps) V4L_WPS_BWD(true, false, true, true, 0);
-    else if (head_ext && tok0_ext) V4L_WPS_BWD(false, false, false, false, 0);
-    else if (head_ext) V4L_WPS_BWD(false, false, false, true, 0);
-    else if (tok0_ext) V4L_WPS_BWD(false, false, true, false, 0);
-    else V4L_WPS_BWD(false, false, true, true, 0);
+    switch (r.family) {
+      case LayerFamily::WPS_OPT_VIS:
+        if (m_out && m_in) V4L_WPS_BWD(false, 2, true, true, 3);
+        else if (m_in) V4L_WPS_BWD(false, 2, true, true, 2);
+        else V4L_WPS_BWD(false, 2, true, true, 1);
+        break;
+      case LayerFamily::WPS_OPT:
+        if (m_out && m_in) V4L_WPS_BWD(false, false, true, true, 3);
+        else if (m_in) V4L_WPS_BWD(false, false, true, true, 2);
+        else V4L_WPS_BWD(false, false, true, true, 1);
+        break;
+      case LayerFamily::WPS_VIS17:
+        if (taps) V4L_WPS_BWD(true, true, true, true, 0);
+        else V4L_WPS_BWD(false, true, true, true, 0);
+        break;
+      case LayerFamily::WPS_VIS:  // native 16 tokens: no 17th-token side blocks (wa.l[].tk = null below)
+        V4L_WPS_BWD(false, 2, true, true, 0);
+        break;
+      default:  // WPS_PLAIN
+        if (taps) V4L_WPS_BWD(true, false, true, true, 0);
+        else if (head_ext && tok0_ext) V4L_WPS_BWD(false, false, false, false, 0);
+        else if (head_ext) V4L_WPS_BWD(false, false, false, true, 0);
+        else if (tok0_ext) V4L_WPS_BWD(false, false, true, false, 0);
+        else V4L_WPS_BWD(false, false, true, true, 0);
+    }
 #undef V4L_WPS_BWD
     V4L_LAUNCH_CHECK();
     // the layers' weight-grads: one partial slab set per run of WPS_SPLIT samples
@@ -2016,7 +2000,7 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
       const TLayer& t = layers[li];
       const Lin* ls[4] = {&t.inproj, &t.outproj, &t.ff1, &t.ff2};
       wa.l[li].wg = ws + L.wps_wg[li];
-      wa.l[li].tk = ((vis_wps && !taps && !vis17_forced()) || vis_opt) ? nullptr : ws + L.wps_tk[li];
+      wa.l[li].tk = (r.family == LayerFamily::WPS_VIS || vis_opt) ? nullptr : ws + L.wps_tk[li];
       for (int m = 0; m < 4; ++m) {
         const Lin& Lm = *ls[m];
         const int64_t sf = ((int64_t)wa.nsplit * Lm.N * Lm.K + 63) / 64 * 64, bf = ((int64_t)wa.nsplit * Lm.N + 63) / 64 * 64;
@@ -2042,18 +2026,8 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
     cx.wps_pending = true;
     cx.wps_used = true;
   }
-  for (int l = c.n_layers - 1; l >= 0 && fused_bwd && !wps; l -= stacked ? 2 : 1) {
+  for (int l = c.n_layers - 1; l >= 0 && r.block(); l -= stacked ? 2 : 1) {
     static int spw = 4;  // samples per block: 4 (80 MFMA rows, 1 block per CU) or 2 (48 rows, 2 blocks per CU): measured equal
-    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 4, false, false, 1>>(BwdLayLds<T, 4>::bytes));
-    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 4, true, false, 1>>(BwdLayLds<T, 4>::bytes));
-    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 4, false, true, 1>>(BwdLayLds<T, 4>::bytes));
-    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 4, true, true, 1>>(BwdLayLds<T, 4>::bytes));
-    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 4, true, true, 2>>(BwdLayLds<T, 4>::bytes));
-    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 2, false, false, 1>>(BwdLayLds<T, 2>::bytes));
-    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 2, true, false, 1>>(BwdLayLds<T, 2>::bytes));
-    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 2, false, true, 1>>(BwdLayLds<T, 2>::bytes));
-    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 2, true, true, 1>>(BwdLayLds<T, 2>::bytes));
-    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, 2, true, true, 2>>(BwdLayLds<T, 2>::bytes));
     const int nblk = cdiv(n, spw);
     const int nl = stacked ? 2 : 1;
     const T* base = (const T*)packed;
@@ -2076,7 +2050,7 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
       e.o_dz2 = ws + b.dz2; e.o_df = ws + b.df; e.o_dz1 = ws + b.dz1; e.o_dqkv = ws + b.dqkv; e.o_dx = ws + L.dxl[li];
       e.gp2 = part; e.bp2 = part + (int64_t)nblk * TD; e.gp1 = part + 2 * (int64_t)nblk * TD; e.bp1 = part + 3 * (int64_t)nblk * TD;
     }
-    const bool hd_on = fused_head && l == c.n_layers - 1, tl_on = fused_tail && l - (nl - 1) == 0;
+    const bool hd_on = r.heads_in && l == c.n_layers - 1, tl_on = r.tail_in && l - (nl - 1) == 0;
     BwdHead bh;
     memset(&bh, 0, sizeof(bh));
     if (hd_on) {
@@ -2093,25 +2067,23 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
     g_op = "layer";
     const double fl = nl * 4.0 * n * 872576.0 + (hd_on ? 2.0 * n * 2 * (16 * 256 + 256 * 256 + 256 * 128) : 0.0) +
                       (tl_on ? 2.0 * n * (64 * 256 + 256 * 256 + 16 * 64 * 64) : 0.0);
-#define V4L_BWD_LAYER(H, TL)                                                                                              \
+#define V4L_BWD_LAYER(SPW_, H_, TL_, NL_, LABEL_)                                                                         \
   do {                                                                                                                    \
-    const char* kn = H ? (TL ? "fused_layer_bwd_head_tail" : "fused_layer_bwd_head")                                      \
-                       : (TL ? "fused_layer_bwd_tail" : "fused_layer_bwd");                                               \
-    if (spw == 2)                                                                                                         \
-      V4L_KLAUNCH(kn, fl, s, (bwd_layer_kernel<T, 2, H, TL, 1>), dim3(nblk), dim3(256), (BwdLayLds<T, 2>::bytes), s, d, bh, bt, n); \
-    else                                                                                                                  \
-      V4L_KLAUNCH(kn, fl, s, (bwd_layer_kernel<T, 4, H, TL, 1>), dim3(nblk), dim3(256), (BwdLayLds<T, 4>::bytes), s, d, bh, bt, n); \
+    V4L_HIP_CHECK(lds_limit<&bwd_layer_kernel<T, SPW_, H_, TL_, NL_>>(BwdLayLds<T, SPW_>::bytes));                        \
+    V4L_KLAUNCH(LABEL_, fl, s, (bwd_layer_kernel<T, SPW_, H_, TL_, NL_>), dim3(nblk), dim3(256), (BwdLayLds<T, SPW_>::bytes), s, d, bh, \
+                bt, n);                                                                                                   \
   } while (0)
-    if (stacked) {
-      if (spw == 2)
-        V4L_KLAUNCH("fused_layer_bwd_stack", fl, s, (bwd_layer_kernel<T, 2, true, true, 2>), dim3(nblk), dim3(256), (BwdLayLds<T, 2>::bytes), s, d, bh, bt, n);
-      else
-        V4L_KLAUNCH("fused_layer_bwd_stack", fl, s, (bwd_layer_kernel<T, 4, true, true, 2>), dim3(nblk), dim3(256), (BwdLayLds<T, 4>::bytes), s, d, bh, bt, n);
-    } else
-    if (hd_on && tl_on) V4L_BWD_LAYER(true, true);
-    else if (hd_on) V4L_BWD_LAYER(true, false);
-    else if (tl_on) V4L_BWD_LAYER(false, true);
-    else V4L_BWD_LAYER(false, false);
+#define V4L_BWD_LAYERS(SPW_)                                                                                              \
+  do {                                                                                                                    \
+    if (stacked) V4L_BWD_LAYER(SPW_, true, true, 2, "fused_layer_bwd_stack");                                             \
+    else if (hd_on && tl_on) V4L_BWD_LAYER(SPW_, true, true, 1, "fused_layer_bwd_head_tail");                             \
+    else if (hd_on) V4L_BWD_LAYER(SPW_, true, false, 1, "fused_layer_bwd_head");                                          \
+    else if (tl_on) V4L_BWD_LAYER(SPW_, false, true, 1, "fused_layer_bwd_tail");                                          \
+    else V4L_BWD_LAYER(SPW_, false, false, 1, "fused_layer_bwd");                                                         \
+  } while (0)
+    if (spw == 2) V4L_BWD_LAYERS(2);
+    else V4L_BWD_LAYERS(4);
+#undef V4L_BWD_LAYERS
 #undef V4L_BWD_LAYER
     V4L_LAUNCH_CHECK();
     for (int kk = 0; kk < nl; ++kk) {
@@ -2119,16 +2091,7 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
       const TLayer& t = layers[li];
       const LayerWs& w = L.lw[li];
       const LayerBw& b = L.lb[li];
-      const float* part = d.l[kk].gp2;
-      const int lnp[4] = {t.ln2.g, t.ln2.b, t.ln1.g, t.ln1.b};
-      for (int k = 0; k < 4; ++k) {
-        RedDesc r;
-        memset(&r, 0, sizeof(r));
-        r.slab = part + (int64_t)k * nblk * TD;
-        r.dW = grads + params[lnp[k]].goff;
-        r.nsplit = nblk; r.N = 1; r.K = TD; r.Npad = 1; r.Kpad = TD; r.Ktorch = TD;
-        red.push_back(r);
-      }
+      reduce_ln_partials(t, d.l[kk].gp2, nblk);
       const float* xin = sizeof(T) == 2 ? ws + w.xin : ws + L.x[li];
       if ((rc = lin_wgrad_wide(cx, t.ff2, ws + b.dz2, ws + w.f, R))) return rc;
       if ((rc = lin_wgrad_wide(cx, t.ff1, ws + b.df, ws + w.x1, R))) return rc;
@@ -2136,7 +2099,7 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
       if ((rc = lin_wgrad_wide(cx, t.inproj, ws + b.dqkv, xin, R))) return rc;
     }
   }
-  for (int l = c.n_layers - 1; l >= 0 && !fused_bwd && !vis_wps && !opt_wps; --l) {
+  for (int l = c.n_layers - 1; l >= 0 && r.family == LayerFamily::LAYER_BY_LAYER; --l) {
     const TLayer& t = layers[l];
     const LayerWs& w = L.lw[l];
     const LayerBw& b = L.lb[l];
@@ -2188,10 +2151,7 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
     dx = ws + L.dx0raw;
     x0 = ws + L.x0raw;
   }
-  // (the option variants: use_pytorch_encoder alone leaves the encoder-side data-grads inside the layers' launch like the plain
-  // net; token_norm takes them layer by layer from token_ln's backward)
-  const bool tail_in = fused_tail || (opt_wps && !c.token_norm && (vis || wps_tail_shape()));
-  if (tail_in && !vis) {  // data-grads done by layer 0's launch: register the four weight-grads
+  if (r.tail_in && !vis) {  // data-grads done by layer 0's launch: register the four weight-grads
     const Act& last = eacts[ne - 1];
     if ((rc = lin_wgrad<T>(cx, proj, dense(dx, NTOK * TD, n, TD, nullptr, 0, x0), dense(last.p, last.ld, n, last.w), last.w)))
       return rc;
@@ -2199,10 +2159,10 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
     if ((rc = lin_wgrad<T>(cx, enc[0], dense(dehp[0], 256, n, 256), sin, sin.K))) return rc;
     if ((rc = lin_wgrad<T>(cx, upconv, dense(dx, TD, n * 16, TD, nullptr, 1), dense(ws + L.c3, 64, n * 16, 64), 64))) return rc;
   }
-  if (vis_wps || (vis_opt && tail_in)) {  // the up-conv data-grad came out of the layer launch (dc3): its weight-grad reads rows 1..16 of the 17-row stride
+  if (r.tail_in && vis) {  // the up-conv data-grad came out of the layer launch (dc3): its weight-grad reads rows 1..16 of the 17-row stride
     if ((rc = lin_wgrad<T>(cx, upconv, dense(dx, TD, n * 16, TD, nullptr, 1), dense(ws + L.c3, 64, n * 16, 64), 64))) return rc;
   }
-  if (!tail_in && !vis) {  // token 0 -> state_projector -> encoder MLP
+  if (!r.tail_in && !vis) {  // token 0 -> state_projector -> encoder MLP
     const Act& last = eacts[ne - 1];
     ADense yp = dense(dx, NTOK * TD, n, TD, nullptr, 0, x0);
     if ((rc = lin_wgrad<T>(cx, proj, yp, dense(last.p, last.ld, n, last.w), last.w))) return rc;
@@ -2212,7 +2172,7 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
     if ((rc = lin_dgrad<T>(cx, proj, yp, ep))) return rc;
     if ((rc = chain_bwd<T>(cx, enc.data(), ne, sin, eacts, dense(ws + L.dhc, last.w, n, last.w), dehp, nullptr))) return rc;
   }
-  if (!tail_in && !vis_wps) {  // tokens 1..16 (vision-only: all 16) -> depth_up_conv -> conv stack
+  if (!r.tail_in) {  // tokens 1..16 (vision-only: all 16) -> depth_up_conv -> conv stack
     ADense yu = dense(dx, TD, n * 16, TD, nullptr, (vis && !vis_opt) ? 0 : 1);  // (1: rows 1..16 of 17-row slots)
     if ((rc = lin_wgrad<T>(cx, upconv, yu, dense(ws + L.c3, 64, n * 16, 64), 64))) return rc;
     Epi ep = mk_epi(ws + L.dc3, 64, 64);
@@ -2261,12 +2221,6 @@ enum class StepRoute {
   STACK_F32ENC,    // LocoTransformer, fp32: rollout_encoder_kernel + rollout_stack_kernel
   GENERAL,         // layer by layer (forward_t of each net) + act_finish_kernel
 };
-// the shapes the fused kernels are specialised for: the proprio MLP 256-256 on at most 128 inputs, heads 256-256, 4 x 64 x 64 depth
-static bool mlp_256(const v4l_net_cfg& c) {
-  return c.n_enc_hidden == 2 && c.enc_hidden[0] == 256 && c.enc_hidden[1] == 256 && c.state_dim <= 128;
-}
-static bool head_256(const v4l_net_cfg& c) { return c.n_head_hidden == 2 && c.head_hidden[0] == 256 && c.head_hidden[1] == 256; }
-static bool depth_64(const v4l_net_cfg& c) { return c.in_channels == 4 && c.img_hw == 64; }
 static StepRoute step_route(const v4l_actor* a, int shared_encoder) {
   const v4l_net *pf = a->pf, *vf = a->vf;
   const v4l_net_cfg &p = pf->cfg, &v = vf->cfg;
@@ -3410,7 +3364,7 @@ int v4l_trainer_critic_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, cons
     return rc;
   const float inv_n = 1.f / ((float)n * (float)hp->world_size);
   const float gscale = v4l_net_grad_scale(vf, n);
-  if (vf->fb_ok()) {
+  if (vf->layer_route().fb_allowed) {
     // round 6: encoder forward, then ONE launch for layers + heads forward, the loss rows and the backward (csrc/wps_fb.h)
     { PhaseScope ps("vf.fwd");
     if ((rc = net_forward_encoder(vf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, stream))) return rc; }
@@ -3436,8 +3390,7 @@ int v4l_trainer_critic_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, cons
     // more (21 us launch) than it saves — measured with tools/update_timeline.py, profiles/r4_update_timeline.txt — so the
     // critic keeps the in-kernel heads unless V4L_WPS_HEAD_EXT_CRITIC=1.
     RowsChain hc;
-    const bool ext_critic = sw_on("V4L_WPS_HEAD_EXT_CRITIC");  // (read per call: tests switch it)
-    const bool ext = ext_critic && vf->heads_ext(tr->ws, n, &hc) != 0;
+    const bool ext = vf->heads_ext(tr->ws, n, &hc, true) != 0;
     const dim3 blk(n >= 512 ? 1024 : 256);
     if (ext) {
       const bool big = n >= 512;
@@ -3527,7 +3480,7 @@ int v4l_trainer_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const
   }
   if ((rc = v4l_net_pack(pf, stream))) return rc;  // the critic step moved the shared encoder
   // round 6: with log pi_old stored at action time the policy's pass is encoder forward + ONE fused launch (csrc/wps_fb.h)
-  const bool fb = stored && !pf->cfg.tanh_action && pf->fb_ok();
+  const bool fb = stored && !pf->cfg.tanh_action && pf->layer_route().fb_allowed;
   { PhaseScope ps("pf.fwd");
   if (fb) rc = net_forward_encoder(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, stream);
   else rc = v4l_net_forward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, 1, stream);
