@@ -92,12 +92,17 @@ extern "C" {
                         operand that overflowed anywhere in a V4L_F16 pass ends up here through the losses / gradient norms);
                         [23] = V4L_F16: loss-gradient elements of this update clamped at +-V4L_F16_GRAD_CLAMP (0 otherwise) */
 #define V4L_OUT_LD 16 /* row stride of head outputs (action mean / value), zero padded */
+#define V4L_MAX_ACT 16 /* widest action vector a policy may have. The reference's GaussianContPolicy* classes take any
+                          output_shape; its joint-space environments take one action per motor, a1.NUM_MOTORS = 12
+                          (vision4leg/envs/locomotion_gym_env.py:195-214, locomotion_gym_env_with_rich_information.py:255-273,
+                          env_builder.py:236-258), the shipped MPC configs 6. 16 is the padded head row (V4L_OUT_LD): every
+                          kernel that files a head output or its gradient already works on 16 columns */
 
 typedef struct v4l_net_cfg {
   int kind;            /* V4L_NET_*                                                                      */
   int compute;         /* V4L_F32 | V4L_BF16 | V4L_F16                                                   */
   int state_dim;       /* S: proprio length (state_input_dim, starter/ppo_locotransformer.py:81)         */
-  int out_dim;         /* A for a policy, 1 for a value net                                              */
+  int out_dim;         /* A for a policy (1 .. V4L_MAX_ACT), 1 for a value net                           */
   int in_channels;     /* 4 (depth stack); ignored for V4L_NET_MLP                                       */
   int img_hw;          /* 64                                                                             */
   int n_enc_hidden;    /* encoder.hidden_shapes / MLPBase hidden_shapes (base.py:8-44)                   */
@@ -186,7 +191,7 @@ int v4l_net_backward(v4l_net* net, const float* state_dev, const void* image_dev
 
 /* GaussianContPolicyBase.{forward,explore,update} post-processing (policies/continuous_policy.py:85-146,
  * 486-492): contiguous mean/std [n][A], clamped log_std [A], ent [n], and log_prob [n] of acts_dev ([n][A])
- * when acts_dev != NULL. meanp_dev is v4l_net_out_ptr of the policy net. */
+ * when acts_dev != NULL. meanp_dev is v4l_net_out_ptr of the policy net. 1 <= A <= V4L_MAX_ACT (this one and the next). */
 int v4l_gauss_head(const float* meanp_dev, const float* logstd_dev, const float* acts_dev, int n, int A,
                    float* mean_dev, float* std_dev, float* logstd_c_dev, float* ent_dev, float* logp_dev,
                    void* stream);

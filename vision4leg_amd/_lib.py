@@ -17,6 +17,7 @@ V4L_STATS = 24
 ST_NONFINITE = 22   # record slot: number of NaN / Inf among the 18 logged scalars of an update
 ST_F16_SAT = 23     # record slot: V4L_F16 — loss-gradient elements of the update clamped at +-V4L_F16_GRAD_CLAMP
 V4L_OUT_LD = 16
+V4L_MAX_ACT = 16   # widest action vector of a policy (include/v4l_hip.h)
 V4L_BUCKET_TAIL = 8   # scalars behind the gradients of an all-reduce bucket
 V4L_COMM_ID_BYTES = 128
 

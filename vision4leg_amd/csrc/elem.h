@@ -9,7 +9,7 @@ namespace v4l {
 
 constexpr int NTOK = 17;   // 1 proprio token + 4x4 depth patches (torchrl/networks/base.py:544,617-622)
 constexpr int TD = 64;     // token_dim (torchrl/networks/base.py:504)
-constexpr int OUT_LD = 16; // row stride of head outputs / their grads (A=6 or 1, zero padded)
+constexpr int OUT_LD = 16; // row stride of head outputs / their grads (A <= V4L_MAX_ACT or 1, zero padded)
 constexpr float LOG_SIG_MAX = 2.f, LOG_SIG_MIN = -5.f;  // torchrl/policies/continuous_policy.py:8-9
 constexpr float HALF_LOG_2PI = 0.91893853320467274178f;
 
@@ -595,12 +595,22 @@ struct ActorArgs {
   float gscale;     // the dmean rows leave multiplied by this (v4l_net_grad_scale: 1, or V4L_F16's power of two); d log sigma never does
   int tanh_action;  // TanhNormal policies: log-probs of the stored (post-tanh) actions through atanh, distribution.py:38-51
 };
-struct ActorDims { float ls[8], sg[8], lsg[8], tls[8], tsg[8], tlsg[8]; float ent; };
-__device__ __forceinline__ ActorDims actor_dims(const ActorArgs& p) {
-  ActorDims d;
+// ACT_CAP: the compile-time action capacity of the per-row code below: 8 (every shipped config: the MPC action space, A = 6)
+// or V4L_MAX_ACT = 16 (joint-space control, one action per motor: A = 12). The per-dimension arrays are per-thread state: at
+// capacity 8 they fit the 128 VGPRs a 1024-thread block leaves a thread (121 used, no spill); at capacity 16 they do not (the
+// compiler spills 88 VGPRs to 228 B of scratch per lane under that bound — DESIGN.md 4.5), so a policy with A <= 8 runs the
+// capacity-8 instantiation and pays nothing for the wider one.
+constexpr int ACT_CAP_NARROW = 8;
+static_assert(V4L_MAX_ACT == OUT_LD, "the widest policy fills the padded head row exactly");
+constexpr int act_cap(int A) { return A <= ACT_CAP_NARROW ? ACT_CAP_NARROW : V4L_MAX_ACT; }
+template <int CAP> struct ActorDimsT { float ls[CAP], sg[CAP], lsg[CAP], tls[CAP], tsg[CAP], tlsg[CAP]; float ent; };
+typedef ActorDimsT<ACT_CAP_NARROW> ActorDims;
+template <int CAP = ACT_CAP_NARROW>
+__device__ __forceinline__ ActorDimsT<CAP> actor_dims(const ActorArgs& p) {
+  ActorDimsT<CAP> d;
   d.ent = 0.f;
 #pragma unroll
-  for (int a = 0; a < 8; ++a) {
+  for (int a = 0; a < CAP; ++a) {
     d.ls[a] = d.sg[a] = d.lsg[a] = d.tls[a] = d.tsg[a] = d.tlsg[a] = 0.f;
     if (a < p.A) {
       d.ls[a] = fminf(fmaxf(p.logstd[a], LOG_SIG_MIN), LOG_SIG_MAX);
@@ -616,23 +626,26 @@ __device__ __forceinline__ ActorDims actor_dims(const ActorArgs& p) {
 // d(log pi)/d(mean) (dm) and d(log pi)/d(log sigma) + 1 (z2)
 // TANH: compiled in only for TanhNormal policies (as a run-time flag the atanh / correction logs were evaluated speculatively for
 // every policy: the single-block statistics launch went from 14 to 36 us)
-struct ActorRow { float lp, ratio, sur, dlp, dm[8], z2[8]; };
-template <bool TANH>
-__device__ __forceinline__ ActorRow actor_row(const ActorArgs& p, const ActorDims& D, int i, int slot, float amean, float astd) {
-  ActorRow o;
-  float lp = 0.f, lpo = 0.f, mu[8], tmu[8];
-  {  // the padded [OUT_LD] rows are 64-byte aligned: two 16-byte loads per row instead of A strided scalar ones
-    const float4 m0 = *reinterpret_cast<const float4*>(p.mean + (int64_t)i * OUT_LD);
-    const float4 m1 = *reinterpret_cast<const float4*>(p.mean + (int64_t)i * OUT_LD + 4);
-    mu[0] = m0.x; mu[1] = m0.y; mu[2] = m0.z; mu[3] = m0.w; mu[4] = m1.x; mu[5] = m1.y; mu[6] = m1.z; mu[7] = m1.w;
-    if (p.logp_old == nullptr) {
-      const float4 t0 = *reinterpret_cast<const float4*>(p.tmean + (int64_t)i * OUT_LD);
-      const float4 t1 = *reinterpret_cast<const float4*>(p.tmean + (int64_t)i * OUT_LD + 4);
-      tmu[0] = t0.x; tmu[1] = t0.y; tmu[2] = t0.z; tmu[3] = t0.w; tmu[4] = t1.x; tmu[5] = t1.y; tmu[6] = t1.z; tmu[7] = t1.w;
-    }
-  }
+template <int CAP> struct ActorRowT { float lp, ratio, sur, dlp, dm[CAP], z2[CAP]; };
+typedef ActorRowT<ACT_CAP_NARROW> ActorRow;
+// a padded [OUT_LD] row's first CAP floats: the rows are 64-byte aligned, 16-byte loads instead of A strided scalar ones
+template <int CAP>
+__device__ __forceinline__ void actor_load_row(const float* __restrict__ row, float (&v)[CAP]) {
 #pragma unroll
-  for (int a = 0; a < 8; ++a) {
+  for (int q = 0; q < CAP / 4; ++q) {
+    const float4 m = *reinterpret_cast<const float4*>(row + 4 * q);
+    v[4 * q] = m.x; v[4 * q + 1] = m.y; v[4 * q + 2] = m.z; v[4 * q + 3] = m.w;
+  }
+}
+template <bool TANH, int CAP = ACT_CAP_NARROW>
+__device__ __forceinline__ ActorRowT<CAP> actor_row(const ActorArgs& p, const ActorDimsT<CAP>& D, int i, int slot, float amean,
+                                                    float astd) {
+  ActorRowT<CAP> o;
+  float lp = 0.f, lpo = 0.f, mu[CAP], tmu[CAP];
+  actor_load_row(p.mean + (int64_t)i * OUT_LD, mu);
+  if (p.logp_old == nullptr) actor_load_row(p.tmean + (int64_t)i * OUT_LD, tmu);
+#pragma unroll
+  for (int a = 0; a < CAP; ++a) {
     if (a < p.A) {
       const float act = p.acts[(int64_t)slot * p.A + a];
       const float x = TANH ? tanh_pre(act) : act;
@@ -664,37 +677,45 @@ __device__ __forceinline__ ActorRow actor_row(const ActorArgs& p, const ActorDim
   return o;
 }
 // the row's d(loss)/d(mean) as the backward gets it (statistics block and chain blocks: the same bits)
-__device__ __forceinline__ void actor_dmean_row(const ActorRow& o, float gscale, float (&dmr)[8], int& sat) {
+template <int CAP>
+__device__ __forceinline__ void actor_dmean_row(const ActorRowT<CAP>& o, float gscale, float (&dmr)[CAP], int& sat) {
 #pragma unroll
-  for (int a = 0; a < 8; ++a) dmr[a] = grad_out(o.dlp * o.dm[a], gscale, sat);
+  for (int a = 0; a < CAP; ++a) dmr[a] = grad_out(o.dlp * o.dm[a], gscale, sat);
 }
-template <bool TANH>
-__device__ __forceinline__ void actor_loss_body(const ActorArgs& p) {
-  __shared__ float sdl[16][8];
-  const int n = p.n, A = p.A;
-  const ActorDims D = actor_dims(p);
-  float dl[8];
+// files a row's d(loss)/d(mean) in a padded row of >= OUT_LD floats; zero_rest: the columns from CAP on as zeros too
+template <int CAP>
+__device__ __forceinline__ void actor_store_dmean(float* __restrict__ row, const float (&dmr)[CAP], bool zero_rest) {
+  float4* drow = reinterpret_cast<float4*>(row);
 #pragma unroll
-  for (int a = 0; a < 8; ++a) dl[a] = 0.f;
+  for (int q = 0; q < CAP / 4; ++q) drow[q] = float4{dmr[4 * q], dmr[4 * q + 1], dmr[4 * q + 2], dmr[4 * q + 3]};  // dm[a >= A] == 0
+  if (zero_rest) {
+#pragma unroll
+    for (int q = CAP / 4; q < OUT_LD / 4; ++q) drow[q] = float4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+template <bool TANH, int CAP = ACT_CAP_NARROW>
+__device__ __forceinline__ void actor_loss_body(const ActorArgs& p) {
+  __shared__ float sdl[16][CAP];
+  const int n = p.n, A = p.A;
+  const ActorDimsT<CAP> D = actor_dims<CAP>(p);
+  float dl[CAP];
+#pragma unroll
+  for (int a = 0; a < CAP; ++a) dl[a] = 0.f;
   const float amean = p.st[ST_ADV_MEAN], astd = p.st[ST_ADV_STD];
   double s_lp = 0.0, s_lp2 = 0.0, s_sur = 0.0;
   int sat = 0;
   float lp_mx = -INFINITY, lp_mn = INFINITY, r_mx = -INFINITY, r_mn = INFINITY;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
     const int slot = p.rowidx ? p.rowidx[i] : i;
-    const ActorRow o = actor_row<TANH>(p, D, i, slot, amean, astd);
+    const ActorRowT<CAP> o = actor_row<TANH, CAP>(p, D, i, slot, amean, astd);
     s_sur += o.sur;
     {
-      float4* drow = reinterpret_cast<float4*>(p.dmean + (int64_t)i * OUT_LD);
-      float dmr[8];
+      float dmr[CAP];
       actor_dmean_row(o, p.gscale, dmr, sat);
-      drow[0] = float4{dmr[0], dmr[1], dmr[2], dmr[3]};  // dm[a >= A] == 0
-      drow[1] = float4{dmr[4], dmr[5], dmr[6], dmr[7]};
-      drow[2] = float4{0.f, 0.f, 0.f, 0.f};
-      drow[3] = float4{0.f, 0.f, 0.f, 0.f};
+      actor_store_dmean(p.dmean + (int64_t)i * OUT_LD, dmr, true);
     }
 #pragma unroll
-    for (int a = 0; a < 8; ++a)
+    for (int a = 0; a < CAP; ++a)
       if (a < A) dl[a] += o.dlp * (o.z2[a] - 1.f);
     s_lp += o.lp; s_lp2 += (double)o.lp * o.lp;
     lp_mx = fmaxf(lp_mx, o.lp); lp_mn = fminf(lp_mn, o.lp);
@@ -705,7 +726,7 @@ __device__ __forceinline__ void actor_loss_body(const ActorArgs& p) {
   // reduce dlogstd over the block
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
-  for (int a = 0; a < 8; ++a) {
+  for (int a = 0; a < CAP; ++a) {
     float v = wave_sum(dl[a]);
     if (lane == 0) sdl[w][a] = v;
   }
@@ -730,20 +751,20 @@ __device__ __forceinline__ void actor_loss_body(const ActorArgs& p) {
     if (p.gscale != 1.f) st[ST_F16_SAT] += (float)r2.s2;
     double m = 0.0; float mx = -INFINITY, mn = INFINITY;
 #pragma unroll
-    for (int a = 0; a < 8; ++a)
+    for (int a = 0; a < CAP; ++a)
       if (a < A) { m += D.ls[a]; mx = fmaxf(mx, D.ls[a]); mn = fminf(mn, D.ls[a]); }
     m /= A;
     double q = 0.0;
 #pragma unroll
-    for (int a = 0; a < 8; ++a)
+    for (int a = 0; a < CAP; ++a)
       if (a < A) q += (D.ls[a] - m) * (D.ls[a] - m);
     st[ST_LS_MEAN] = (float)m;
     st[ST_LS_STD] = A > 1 ? (float)sqrt(q / (A - 1)) : NAN;
     st[ST_LS_MAX] = mx; st[ST_LS_MIN] = mn;
   }
 }
-template <bool TANH>
-__global__ __launch_bounds__(1024) void actor_loss_kernel(ActorArgs p) { actor_loss_body<TANH>(p); }
+template <bool TANH, int CAP>
+__global__ __launch_bounds__(1024) void actor_loss_kernel(ActorArgs p) { actor_loss_body<TANH, CAP>(p); }
 #pragma clang fp contract(fast)
 
 // Gaussian head post-processing for the policy API (continuous_policy.py:85-146,486-492): from the padded

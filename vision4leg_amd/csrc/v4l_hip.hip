@@ -827,7 +827,8 @@ int v4l_net::build() {
   const v4l_net_cfg& c = cfg;
   V4L_REQUIRE(c.kind >= V4L_NET_MLP && c.kind <= V4L_NET_LOCO_VIS, "v4l_net_create: unknown net kind %d", c.kind);
   V4L_REQUIRE(c.compute == V4L_F32 || c.compute == V4L_BF16 || c.compute == V4L_F16, "v4l_net_create: unknown compute mode %d", c.compute);
-  V4L_REQUIRE(c.out_dim > 0 && c.out_dim <= 8, "v4l_net_create: 1<=out_dim<=8 required");
+  V4L_REQUIRE(c.out_dim > 0 && c.out_dim <= V4L_MAX_ACT, "v4l_net_create: 1<=out_dim<=%d (V4L_MAX_ACT) required, got %d", V4L_MAX_ACT,
+              c.out_dim);
   if (vis_only())  // vision-only nets have no proprio branch: the observation row is the depth stack alone
     V4L_REQUIRE(c.state_dim == 0 && c.n_enc_hidden == 0, "v4l_net_create: vision-only nets take state_dim 0 and no encoder MLP");
   else
@@ -1119,7 +1120,9 @@ LayerRoute v4l_net::layer_route(bool whole_pass) const {
     r.heads_in = r.tail_in = true;
     r.heads_ext_allowed = !head_in && !r.taps;
     r.heads_ext_critic = r.heads_ext_allowed && ext_critic;
-    r.fb_allowed = r.heads_ext_allowed && !c.max_pool && !no_fb && !ext_critic;
+    // (the fused forward-loss-backward launch holds a row's action dimensions in capacity-8 arrays and is not widened: one wave
+    // per SIMD at 512 registers, launch time grows with code size. A wider policy takes the TanhNormal policies' route.)
+    r.fb_allowed = r.heads_ext_allowed && !c.max_pool && !no_fb && !ext_critic && c.out_dim <= ACT_CAP_NARROW;
   } else if (around && !plain) {
     // (use_pytorch_encoder alone leaves the encoder-side data-grads inside the launch like the plain net; token_norm takes them
     // layer by layer from token_ln's backward, another proprio MLP from the layer-0 input gradient)
@@ -2579,11 +2582,18 @@ static int launch_critic_loss_heads(hipStream_t s, const float* values, const fl
               oldv, rowidx, n, inv_n, clipped, clip, dvalues, st, hc, gscale);
   return 0;
 }
-template <typename T, int NW>
+template <typename T, int NW, int CAP>
 static int launch_actor_loss_heads(hipStream_t s, const ActorArgs& aa, const RowsChain& hc) {
-  V4L_HIP_CHECK(lds_limit<&actor_loss_heads_kernel<T, NW>>(RowsChainLds<T, RowsChainCfg<T>::MT>::bytes3));
-  V4L_KLAUNCH("actor_loss", 2.0 * aa.n * (16 * 256 + 256 * 256 + 256 * 128), s, (actor_loss_heads_kernel<T, NW>),
+  V4L_HIP_CHECK(lds_limit<&actor_loss_heads_kernel<T, NW, CAP>>(RowsChainLds<T, RowsChainCfg<T>::MT>::bytes3));
+  V4L_KLAUNCH("actor_loss", 2.0 * aa.n * (16 * 256 + 256 * 256 + 256 * 128), s, (actor_loss_heads_kernel<T, NW, CAP>),
               dim3(1 + cdiv(aa.n, RowsChainCfg<T>::MT * 16)), dim3(NW * 64), (RowsChainLds<T, RowsChainCfg<T>::MT>::bytes3), s, aa, hc);
+  return 0;
+}
+// the statistics-only loss launch: one block
+template <int CAP>
+static int launch_actor_loss(hipStream_t s, const ActorArgs& aa, dim3 blk) {
+  if (aa.tanh_action) V4L_KLAUNCH("actor_loss", 0, s, (actor_loss_kernel<true, CAP>), dim3(1), blk, 0, s, aa);
+  else V4L_KLAUNCH("actor_loss", 0, s, (actor_loss_kernel<false, CAP>), dim3(1), blk, 0, s, aa);
   return 0;
 }
 
@@ -2808,8 +2818,9 @@ int v4l_net_backward(v4l_net* net, const float* state_dev, const void* image_dev
 int v4l_gauss_head(const float* meanp_dev, const float* logstd_dev, const float* acts_dev, int n, int A,
                    float* mean_dev, float* std_dev, float* logstd_c_dev, float* ent_dev, float* logp_dev,
                    void* stream) {
-  V4L_REQUIRE(meanp_dev && logstd_dev && mean_dev && std_dev && logstd_c_dev && ent_dev && n > 0 && A > 0 && A <= 8,
+  V4L_REQUIRE(meanp_dev && logstd_dev && mean_dev && std_dev && logstd_c_dev && ent_dev && n > 0,
               "v4l_gauss_head: bad argument");
+  V4L_REQUIRE(A > 0 && A <= V4L_MAX_ACT, "v4l_gauss_head: 1<=A<=%d (V4L_MAX_ACT) required, got %d", V4L_MAX_ACT, A);
   V4L_REQUIRE(acts_dev == nullptr || logp_dev != nullptr, "v4l_gauss_head: logp_dev is null");
   hipLaunchKernelGGL(gauss_head_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, meanp_dev, logstd_dev,
                      acts_dev, n, A, mean_dev, std_dev, logstd_c_dev, ent_dev, logp_dev, 0, (const float*)nullptr);
@@ -2819,8 +2830,9 @@ int v4l_gauss_head(const float* meanp_dev, const float* logstd_dev, const float*
 int v4l_gauss_head_tanh(const float* meanp_dev, const float* logstd_dev, const float* acts_dev, const float* pre_tanh_dev, int n,
                         int A, float* mean_dev, float* std_dev, float* logstd_c_dev, float* ent_dev, float* logp_dev,
                         void* stream) {
-  V4L_REQUIRE(meanp_dev && logstd_dev && mean_dev && std_dev && logstd_c_dev && ent_dev && n > 0 && A > 0 && A <= 8,
+  V4L_REQUIRE(meanp_dev && logstd_dev && mean_dev && std_dev && logstd_c_dev && ent_dev && n > 0,
               "v4l_gauss_head_tanh: bad argument");
+  V4L_REQUIRE(A > 0 && A <= V4L_MAX_ACT, "v4l_gauss_head_tanh: 1<=A<=%d (V4L_MAX_ACT) required, got %d", V4L_MAX_ACT, A);
   V4L_REQUIRE(acts_dev == nullptr || logp_dev != nullptr, "v4l_gauss_head_tanh: logp_dev is null");
   hipLaunchKernelGGL(gauss_head_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, meanp_dev, logstd_dev,
                      acts_dev, n, A, mean_dev, std_dev, logstd_c_dev, ent_dev, logp_dev, 1, pre_tanh_dev);
@@ -3515,17 +3527,19 @@ int v4l_trainer_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const
     RowsChain hc;
     const bool ext = !pf->cfg.tanh_action && pf->heads_ext(tr->ws, n, &hc) != 0;
     const dim3 blk(n >= 512 ? 1024 : 256);
+    // the per-row code holds its per-dimension state per thread: capacity 8 for every A <= 8, V4L_MAX_ACT above (csrc/elem.h)
+    const bool wide = act_cap(aa.A) != ACT_CAP_NARROW;
     if (ext) {
       const bool big = n >= 512;
       rc = by_compute(pf->cfg.compute, [&](auto tag) -> int {
         typedef typename decltype(tag)::type T;
-        return big ? launch_actor_loss_heads<T, 16>(s, aa, hc) : launch_actor_loss_heads<T, 4>(s, aa, hc);
+        if (wide) return big ? launch_actor_loss_heads<T, 16, V4L_MAX_ACT>(s, aa, hc) : launch_actor_loss_heads<T, 4, V4L_MAX_ACT>(s, aa, hc);
+        return big ? launch_actor_loss_heads<T, 16, ACT_CAP_NARROW>(s, aa, hc) : launch_actor_loss_heads<T, 4, ACT_CAP_NARROW>(s, aa, hc);
       });
-      if (rc) return rc;
     } else {
-      if (aa.tanh_action) V4L_KLAUNCH("actor_loss", 0, s, actor_loss_kernel<true>, dim3(1), blk, 0, s, aa);
-      else V4L_KLAUNCH("actor_loss", 0, s, actor_loss_kernel<false>, dim3(1), blk, 0, s, aa);
+      rc = wide ? launch_actor_loss<V4L_MAX_ACT>(s, aa, blk) : launch_actor_loss<ACT_CAP_NARROW>(s, aa, blk);
     }
+    if (rc) return rc;
   }
   V4L_LAUNCH_CHECK();
   PhaseScope ps("pf.bwd");

@@ -1119,10 +1119,10 @@ __global__ __launch_bounds__(NWAVES * 64) void critic_loss_heads_kernel(const fl
     __syncthreads();
   });
 }
-template <typename T, int NWAVES>
+template <typename T, int NWAVES, int CAP>
 __global__ __launch_bounds__(NWAVES * 64) void actor_loss_heads_kernel(ActorArgs p, RowsChain hc) {
   if (blockIdx.x == 0) {
-    actor_loss_body<false>(p);  // (TanhNormal policies keep the in-kernel heads and actor_loss_kernel<true>)
+    actor_loss_body<false, CAP>(p);  // (TanhNormal policies keep the in-kernel heads and actor_loss_kernel<true>)
     return;
   }
   constexpr int MT = RowsChainCfg<T>::MT;
@@ -1131,19 +1131,17 @@ __global__ __launch_bounds__(NWAVES * 64) void actor_loss_heads_kernel(ActorArgs
   float* dt = reinterpret_cast<float*>(smem);
   const int tid = threadIdx.x, r0 = ((int)blockIdx.x - 1) * MT * 16;
   loss_heads_run<T, NWAVES, false>(hc, dt, r0, p.n, smem, tid, [&]() {
-    for (int idx = tid; idx < MT * 16 * 16; idx += NWAVES * 64)  // columns 8.. (and rows >= n) stay zero
+    for (int idx = tid; idx < MT * 16 * 16; idx += NWAVES * 64)  // columns CAP.. (and rows >= n) stay zero
       *reinterpret_cast<float4*>(dt + (idx >> 4) * LY::LDX + (idx & 15) * 4) = float4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();
     if (tid < MT * 16 && r0 + tid < p.n) {  // one thread per row: the row's d(loss)/d(mean), as block 0 files it in dmean
-      const ActorDims D = actor_dims(p);
+      const ActorDimsT<CAP> D = actor_dims<CAP>(p);
       const int i = r0 + tid, slot = p.rowidx ? p.rowidx[i] : i;
-      const ActorRow o = actor_row<false>(p, D, i, slot, p.st[ST_ADV_MEAN], p.st[ST_ADV_STD]);
-      float4* drow = reinterpret_cast<float4*>(dt + tid * LY::LDX);
-      float dmr[8];
+      const ActorRowT<CAP> o = actor_row<false, CAP>(p, D, i, slot, p.st[ST_ADV_MEAN], p.st[ST_ADV_STD]);
+      float dmr[CAP];
       int sat = 0;
       actor_dmean_row(o, p.gscale, dmr, sat);
-      drow[0] = float4{dmr[0], dmr[1], dmr[2], dmr[3]};
-      drow[1] = float4{dmr[4], dmr[5], dmr[6], dmr[7]};
+      actor_store_dmean(dt + tid * LY::LDX, dmr, false);
     }
     __syncthreads();
   });

@@ -44,6 +44,9 @@ class _HipNetMixin:
     def hip(self):
         if self.__dict__.get("_hip") is None:
             cfg = self._net_cfg()
+            if cfg.out_dim > _lib.V4L_MAX_ACT:
+                raise NotImplementedError("vision4leg_amd: at most %d action dimensions (output_shape) are supported on the "
+                                          "HIP engine (got %d)" % (_lib.V4L_MAX_ACT, cfg.out_dim))
             cfg.tanh_action = int(bool(getattr(self, "tanh_action", False)))  # Gaussian policies (continuous_policy.py)
             self.__dict__["_hip"] = HipNet(self, cfg)
         return self.__dict__["_hip"]
