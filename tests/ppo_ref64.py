@@ -1,8 +1,9 @@
 """Float64 restatement of the last stage of a PPO minibatch update: the critic and actor losses of PPO.update_critic /
 update_actor (torchrl/algo/on_policy/ppo.py:42-123, the advantage normalisation of :142-148), their gradients with respect to
 the network outputs (value column, mean rows) and logstd, the 18 logged scalars, and clip_grad_norm_ followed by torch.optim.Adam
-(ppo.py:73-75,118-120; torch/optim/adam.py::_single_tensor_adam). Everything runs in float64 on the CPU, so it can serve as the
-yardstick of kernels that compute in fp32. tests/test_ref64_cpu.py pins it against oracle/ppo_oracle.py."""
+(ppo.py:73-75,118-120; torch/optim/adam.py::_single_tensor_adam); and of the sampling epilogue of a rollout step (sample_stage:
+std, action, entropy; the stored action's log-prob is log_prob_entropy). Everything runs in float64 on the CPU, so it can serve
+as the yardstick of kernels that compute in fp32. tests/test_ref64_cpu.py pins it against oracle/ppo_oracle.py."""
 import math
 
 import numpy as np
@@ -10,6 +11,9 @@ import torch
 
 LOG_SIG_MIN, LOG_SIG_MAX = -5.0, 2.0  # torchrl/policies/continuous_policy.py:8-9
 EPS32 = 2.0 ** -24                    # fp32 unit roundoff
+# the multiple of sample_stage_bounds the GPU rollout-epilogue tests allow: 4 x what fp32 numpy needs for the stored log-prob
+# (0.58, measured by tests/test_ref64_cpu.py::test_sample_stage_fp32_needs_less_than_the_gate), and no lower than 4
+ROLLOUT_C = 4.0
 
 STAT_KEYS = [
     "advs/mean", "advs/std", "advs/max", "advs/min", "Training/vf_loss", "grad_norm/vf",
@@ -36,6 +40,76 @@ def log_prob_entropy(mean, logstd, acts, tanh_action=False):
     lp = -((acts - mean) ** 2) / (2 * std ** 2) - std.log() - math.log(math.sqrt(2 * math.pi)) - corr
     ent = 0.5 + 0.5 * math.log(2 * math.pi) + torch.log(std)
     return lp.sum(-1), ent.sum(-1), log_std
+
+
+def sample_stage(mean, logstd, eps, tanh_action=False):
+    """The sampling epilogue of a rollout step (GaussianContPolicyBase.explore, continuous_policy.py:85-125; TanhNormal.rsample,
+    policies/distribution.py:61-80) on given standard-normal draws: std = exp(clamp(logstd)), pre = mean + std * eps,
+    action = tanh(pre) | pre, ent = Normal(mean, std).entropy().sum(-1). mean / eps [n][A], logstd [A] (the raw parameter).
+    -> float64 (std [n][A], pre [n][A], action [n][A], ent [n]). The log-prob of a stored action is
+    log_prob_entropy(mean, logstd, action, tanh_action)."""
+    mean, logstd, eps = _d(mean), _d(logstd), _d(eps)
+    log_std = torch.clamp(logstd, LOG_SIG_MIN, LOG_SIG_MAX)
+    std = torch.exp(log_std).unsqueeze(0).expand_as(mean)
+    pre = mean + std * eps
+    action = torch.tanh(pre) if tanh_action else pre
+    ent = (0.5 + 0.5 * math.log(2 * math.pi) + log_std).sum().expand(mean.shape[0])
+    return std, pre, action, ent
+
+
+def sample_stage_bounds(mean, logstd, eps, acts, tanh_action=False):
+    """The magnitudes that enter an fp32 evaluation of sample_stage / log_prob_entropy, per element or row, in float64: an fp32
+    result may differ from the float64 one by c * EPS32 times these (c: the few roundings per operation).
+    - "action" [n][A]: |mean| + |std * eps| (the two addends), tanh: + |action| (tanhf's own rounding)
+    - "ent" [n]: sum_a 1.5 + |log sigma_a| (0.5 + log(2 pi) / 2 + log sigma, summed)
+    - "logp" [n] of the STORED action `acts`: sum_a q + |log sigma| + 1 + |corr| + |term|, q = d^2 / (2 sigma^2), term the a-th
+      summand of log pi (the running sum); tanh rows add the conditioning of the reference's own expressions in fp32:
+      |d| (1 + |z|) / sigma^2 (z = atanh(a) = log((1 + a) / (1 - a)) / 2 carries an absolute error ~ EPS32 (1 + |z|) into d) and
+      1 / (1 - a^2 + 1e-6) (the rounding of 1 - a * a under corr = log(1 - a^2 + 1e-6))."""
+    mean, logstd, eps, acts = _d(mean), _d(logstd), _d(eps), _d(acts)
+    log_std = torch.clamp(logstd, LOG_SIG_MIN, LOG_SIG_MAX).unsqueeze(0).expand_as(mean)
+    std = torch.exp(log_std)
+    b_act = mean.abs() + (std * eps).abs()
+    z, corr = acts, torch.zeros_like(acts)
+    if tanh_action:
+        b_act = b_act + acts.abs()
+        corr = torch.log(1 - acts * acts + 1e-6)
+        z = torch.log((1 + acts) / (1 - acts)) / 2
+    d = z - mean
+    q = d * d / (2 * std * std)
+    term = -q - log_std - math.log(math.sqrt(2 * math.pi)) - corr
+    b_lp = q + log_std.abs() + 1.0 + corr.abs() + term.abs()
+    if tanh_action:
+        b_lp = b_lp + d.abs() * (1 + z.abs()) / (std * std) + 1 / (1 - acts * acts + 1e-6)
+    return {"action": b_act, "ent": (1.5 + log_std.abs()).sum(-1), "logp": b_lp.sum(-1)}
+
+
+def sample_stage_f32(mean, logstd, eps, tanh_action=False):
+    """sample_stage and the stored action's log-prob restated in fp32 numpy, one rounding per operation, the terms summed over
+    a = 0 .. A-1 in order: what a straightforward fp32 implementation computes; measured against the float64 functions above it
+    says which multiple of sample_stage_bounds fp32 arithmetic itself needs. -> fp32 (action [n][A], ent [n], logp [n])."""
+    f = np.float32
+    mean, logstd, eps = (np.asarray(x, dtype=f) for x in (mean, logstd, eps))
+    half_log_2pi = f(0.5 * math.log(2 * math.pi))
+    ls = np.clip(logstd, f(LOG_SIG_MIN), f(LOG_SIG_MAX))
+    sg = np.exp(ls)
+    act = sg[None] * eps + mean
+    x = act
+    if tanh_action:
+        act = np.tanh(act)
+        x = np.log((f(1) + act) / (f(1) - act)) / f(2)
+    d = x - mean
+    lt = -(d * d) / (f(2) * sg * sg)[None] - np.log(sg)[None] - half_log_2pi
+    et = f(0.5) + half_log_2pi + np.log(sg)
+    corr = np.log(f(1) - act * act + f(1e-6)) if tanh_action else None
+    lp, ent = np.zeros(mean.shape[0], dtype=f), np.zeros(mean.shape[0], dtype=f)
+    for a in range(mean.shape[1]):
+        ent = ent + et[a]
+        lp = lp + lt[:, a]
+        if tanh_action:
+            lp = lp - corr[:, a]
+    assert act.dtype == f and lp.dtype == f and ent.dtype == f
+    return act, ent, lp
 
 
 def normalise_advantages(advs):

@@ -34,7 +34,7 @@ def _key(name, mode, shared, dense_split):
 
 def collect(name, mode, shared, dense_split, device):
     """-> (split_supported, ((label, calls, flops), ...)) of one eager step after a warm-up step."""
-    from vision4leg_amd import _lib, engine
+    from vision4leg_amd import engine
     import vision4leg_amd.torchrl.networks as networks
     import vision4leg_amd.torchrl.policies as policies
     case = util.CASES[name]
@@ -54,22 +54,28 @@ def collect(name, mode, shared, dense_split, device):
             parts.append(np.clip(rs.randn(E, 4 * 64 * 64), -2.5, 2.8))
         obs = torch.tensor(np.concatenate(parts, 1), dtype=torch.float32, device=device)
         actor.step(obs)  # (packs the operand-type weights)
-        torch.cuda.synchronize()
-        L = _lib.lib()
-        L.v4l_prof_enable(1)
-        try:
-            actor.step(obs)
-            buf = C.create_string_buffer(1 << 20)
-            L.v4l_prof_collect(buf, len(buf))
-        finally:
-            L.v4l_prof_enable(0)
-        rows = []
-        for line in buf.value.decode().splitlines():
-            label, calls, _, flops = line.split("\t")
-            rows.append((label, int(calls), flops))
-        return actor.split_supported(), tuple(rows)
+        return actor.split_supported(), profile_step(actor, obs)
     finally:
         os.environ.pop("V4L_ROLLOUT_DENSE_SPLIT", None)
+
+
+def profile_step(actor, obs, **kw):
+    """-> ((label, calls, flops), ...) of one eager actor.step(obs, **kw) under the library's profiler."""
+    from vision4leg_amd import _lib
+    torch.cuda.synchronize()
+    L = _lib.lib()
+    L.v4l_prof_enable(1)
+    try:
+        actor.step(obs, **kw)
+        buf = C.create_string_buffer(1 << 20)
+        L.v4l_prof_collect(buf, len(buf))
+    finally:
+        L.v4l_prof_enable(0)
+    rows = []
+    for line in buf.value.decode().splitlines():
+        label, calls, _, flops = line.split("\t")
+        rows.append((label, int(calls), flops))
+    return tuple(rows)
 
 
 @pytest.mark.gpu

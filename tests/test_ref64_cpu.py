@@ -2,7 +2,9 @@
 pinned to the CPU oracle (oracle/ppo_oracle.py, itself pinned to the reference): on a small state-MLP, two PPO updates of the
 oracle in f32 and of the restatement in float64 from the same parameters and batches must log the same 18 scalars, produce the
 same parameter gradients and land on the same parameters, to fp32 noise. The second update runs against the frozen target of
-the first, with a large learning rate, so its ratios leave the clip range on both sides."""
+the first, with a large learning rate, so its ratios leave the clip range on both sides. The sampling epilogue's restatement
+(sample_stage) is pinned to the oracle's Gaussian head, and an fp32 restatement of it measures the constant of the GPU
+rollout-epilogue tests' bounds (ppo_ref64.ROLLOUT_C)."""
 import numpy as np
 import pytest
 import torch
@@ -124,3 +126,63 @@ def test_loss_stage_gradients_match_finite_differences():
             fd = (pl(mean, lp_) - pl(mean, lm_)) / (2 * h)
             assert abs(fd - out["dlogstd"][a].item()) <= 1e-6 * max(1.0, abs(fd)), a
         assert out["dlogstd"][0].item() == 0.0 and out["dlogstd"][3].item() == 0.0
+
+
+@pytest.mark.parametrize("A,tanh", [(16, False), (16, True), (1, False), (6, True)])
+def test_sample_stage_matches_oracle(A, tanh):
+    """ppo_ref64.sample_stage (+ log_prob_entropy on the action it returns) against the oracle's Gaussian head evaluated in
+    float64 on the same numbers (oracle gaussian: clamp / exp / broadcast; oracle log_prob_entropy: takes that std), with a log
+    sigma per column on both sides of both clamp bounds."""
+    rs = np.random.RandomState(60 + A)
+    n = 9
+    mean = torch.tensor(rs.uniform(-1.5, 1.5, (n, A)))
+    eps = torch.tensor(rs.randn(n, A))
+    logstd = torch.tensor(util.logstd_columns(A, tanh)).double()
+    std, pre, action, ent = ref.sample_stage(mean, logstd, eps, tanh)
+    _, ostd, olog_std = orc.gaussian(mean, logstd)
+    assert std.dtype == torch.float64 and torch.equal(std, ostd)
+    opre = mean + ostd * eps
+    assert torch.equal(pre, opre) and torch.equal(action, torch.tanh(opre) if tanh else opre)
+    if tanh:
+        assert action.abs().max().item() < 1.0
+    lp, ent2, log_std = ref.log_prob_entropy(mean, logstd, action, tanh)
+    olp, oent = orc.log_prob_entropy(mean, ostd, action, tanh)
+    assert torch.equal(log_std, olog_std)
+    # (log(exp(x)) against x, sums in another order: float64 rounding)
+    assert (lp - olp.reshape(-1)).abs().max().item() <= 1e-12 * olp.abs().max().item()
+    assert (ent - oent.reshape(-1)).abs().max().item() <= 1e-12 * oent.abs().max().item()
+    assert (ent2 - oent.reshape(-1)).abs().max().item() <= 1e-12 * oent.abs().max().item()
+    # the clamp is what the columns beyond a bound see
+    at = lambda v: ref.sample_stage(mean[:, :1], torch.tensor([v]).double(), eps[:, :1], tanh)[0][0, 0].item()
+    for a, v in enumerate(logstd.tolist()):
+        assert std[0, a].item() == at(min(max(v, -5.0), 2.0))
+
+
+def test_sample_stage_fp32_needs_less_than_the_gate():
+    """What multiple of sample_stage_bounds does fp32 arithmetic itself need? sample_stage_f32 (numpy, one rounding per operation)
+    against the float64 functions, on the log sigma columns the GPU rollout-epilogue tests use, mean ~ U[-1.5, 1.5], eps ~ N(0, 1),
+    257 rows x 16 columns, seeds 0-2, with and without tanh. Measured on the CPU: the stored action's log-prob reaches 0.58
+    (0.43 with tanh) of the bound at c = 1, the entropy 0.27 (0.44), the action 2.7 (1.6: numpy's expf is off by up to one ulp,
+    which is 2 EPS32 of std * eps). The GPU tests' constant is ROLLOUT_C = max(4, 4 x the log-prob's worst ratio): the factor 4
+    is for the device's 1-2 ulp expf / logf / tanhf against numpy's and for other multiply-add orders."""
+    worst = {"action": 0.0, "ent": 0.0, "logp": 0.0}
+    for tanh in (False, True):
+        logstd = util.logstd_columns(16, tanh)
+        for seed in range(3):
+            rs = np.random.RandomState(seed)
+            mean = rs.uniform(-1.5, 1.5, (257, 16)).astype(np.float32)
+            eps = rs.randn(257, 16).astype(np.float32)
+            act, ent, lp = ref.sample_stage_f32(mean, logstd, eps, tanh)
+            if tanh:
+                assert np.abs(act).max() < 1.0   # a condition on the inputs: the float64 log-prob of every stored action is finite
+            _, _, act64, ent64 = ref.sample_stage(mean, logstd, eps, tanh)
+            lp64, _, _ = ref.log_prob_entropy(torch.tensor(mean).double(), torch.tensor(logstd).double(),
+                                              torch.tensor(act).double(), tanh)
+            b = ref.sample_stage_bounds(mean, logstd, eps, act, tanh)
+            for what, got, want in (("action", act, act64), ("ent", ent, ent64), ("logp", lp, lp64)):
+                r = float((np.abs(got - want.numpy()) / (ref.EPS32 * b[what].numpy())).max())
+                worst[what] = max(worst[what], r)
+    print("\n[sample_stage fp32 / bound at c = 1] action %.3f ent %.3f logp %.3f" % (worst["action"], worst["ent"], worst["logp"]))
+    assert np.isfinite(list(worst.values())).all() and worst["logp"] > 0.05  # (a measurement, not zeros)
+    assert ref.ROLLOUT_C >= 4.0 and 4 * worst["logp"] <= ref.ROLLOUT_C
+    assert max(worst.values()) <= ref.ROLLOUT_C  # (fp32 numpy itself passes every gate the GPU tests set)

@@ -1364,7 +1364,7 @@ __global__ __launch_bounds__(512) void rollout_stack_kernel(InfLayerStack stk, I
       } else if (lane == 0) {  // the last block to get here advances the step cursor: every block read it at entry
         __threadfence();
         const unsigned long long done = atomicAdd(reinterpret_cast<unsigned long long*>(&fin.ctl->done), 1ull);
-        if (done == (unsigned long long)(gridDim.x * gridDim.y) - 1) {
+        if (done == 2ull * (unsigned long long)E - 1ull) {  // (one block per (sample, net); the padded blocks of the xcd grid left at entry)
           fin.ctl->done = 0;
           fin.ctl->t = t_step + 1;
         }
