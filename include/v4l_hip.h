@@ -85,6 +85,10 @@ extern "C" {
 #define V4L_NET_LOCO_VIS 4 /* networks.Transformer + TransformerEncoder (depth only: 16 tokens, mean-pooled)
                               nets.py:784-906, base.py:388-494 (starter/ppo_locotransformer_vision_only.py:77-97) */
 
+/* activation of the hidden Linear layers (v4l_net_cfg.activation) */
+#define V4L_ACT_RELU 0
+#define V4L_ACT_TANH 1
+
 #define V4L_MAX_HIDDEN 4
 #define V4L_STATS 24 /* floats per update record; [0..17] = the 18 logger keys of ppo.py:77-92,122-123,142-145;
                         [18..21] shard moments of the advantages (data-parallel exchange); [22] = how many of the 18 are
@@ -128,6 +132,10 @@ typedef struct v4l_net_cfg {
                           (use_pytorch_encoder=True: nets.py:955-963, 884-885, 1012-1013; parameters
                           visual_trans_encoder.layers.N.*, visual_trans_encoder.norm.*); round 5: as token_norm, with the
                           final norm + pooling + heads as launches of their own */
+  int activation;      /* V4L_ACT_*: activation_func of the MLPBase and of the append layers (base.py:13,33,40, nets.py:24,41-44;
+                          the commented switch of every PPO starter). 0 = ReLU, so a zero-initialised config keeps its meaning.
+                          V4L_ACT_TANH: V4L_NET_MLP only — accurate tanhf in the GEMM epilogues and the fused rollout step
+                          kernels, backward through 1 - a^2 of the saved fp32 activation */
 } v4l_net_cfg;
 
 typedef struct v4l_net v4l_net;         /* host-side plan of one network (no device memory)  */

@@ -12,6 +12,7 @@ SRC_DIR = os.path.join(_HERE, "csrc")
 
 V4L_F32, V4L_BF16, V4L_F16 = 0, 1, 2
 V4L_NET_MLP, V4L_NET_CNN, V4L_NET_LOCO, V4L_NET_CNN_VIS, V4L_NET_LOCO_VIS = 0, 1, 2, 3, 4
+V4L_ACT_RELU, V4L_ACT_TANH = 0, 1
 V4L_MAX_HIDDEN = 4
 V4L_STATS = 24
 ST_NONFINITE = 22   # record slot: number of NaN / Inf among the 18 logged scalars of an update
@@ -37,7 +38,7 @@ class NetCfg(C.Structure):
     ("enc_hidden", C.c_int * V4L_MAX_HIDDEN), ("visual_dim", C.c_int), ("token_dim", C.c_int),
     ("n_layers", C.c_int), ("ff_dim", C.c_int), ("n_head_hidden", C.c_int),
     ("head_hidden", C.c_int * V4L_MAX_HIDDEN), ("has_logstd", C.c_int), ("tanh_action", C.c_int), ("max_pool", C.c_int),
-    ("token_norm", C.c_int), ("pytorch_encoder", C.c_int),
+    ("token_norm", C.c_int), ("pytorch_encoder", C.c_int), ("activation", C.c_int),
   ]
 
 

@@ -259,14 +259,38 @@ struct ADgradNHWC {
 
 // ------------------------------------------------------------------------------------ epilogue
 enum { ROWMAP_IDENT = 0, ROWMAP_TOK_DEPTH = 1, ROWMAP_TOK_STATE = 2, ROWMAP_DGRAD = 3 };
+// Epi::act: what follows the bias. Epi::mask_mode: how the saved activation of the layer below gates a data-grad.
+enum { EPI_ACT_NONE = 0, EPI_ACT_RELU = 1, EPI_ACT_TANH = 2 };
+enum { EPI_MASK_RELU = 0, EPI_MASK_TANH = 1 };
+// d tanh = 1 - a^2 of the saved fp32 activation a: exactly 0 where tanh saturated to +-1, never negative (|a| <= 1)
+__device__ __forceinline__ float dtanh(float a) { return fmaf(-a, a, 1.f); }
+// The epilogue's activation and mask steps. TANH is a template argument of the GEMM kernels: the Tanh selectors are compiled
+// into instantiations of their own (launch_nt / launch_nt_deep pick them when an Epi asks for Tanh), so the kernels every
+// ReLU net launches are the code they were before the selectors existed (tanhf's code next to the stores cost the state
+// MLP's update 2 % when it sat behind a run-time branch of the one kernel).
+template <bool TANH> __device__ __forceinline__ float epi_activate(float v, int act) {
+  if constexpr (TANH) {
+    if (act == EPI_ACT_TANH) return tanhf(v);
+    return act == EPI_ACT_RELU ? fmaxf(v, 0.f) : v;
+  } else {
+    return act ? fmaxf(v, 0.f) : v;
+  }
+}
+template <bool TANH> __device__ __forceinline__ float epi_gate(float v, float a, int mask_mode) {
+  if constexpr (TANH) {
+    if (mask_mode == EPI_MASK_TANH) return v * dtanh(a);
+  }
+  return a > 0.f ? v : 0.f;
+}
 
 struct Epi {
   float* C;
   int ldc, M, N;
   const float* bias;  // [N] or null
-  int relu;           // max(x,0) after bias
-  const float* mask;  // null, or multiply by (mask[orow*ldmask+n] > 0): ReLU backward of the layer below
-  int ldmask;
+  int act;            // EPI_ACT_*: max(x,0) / tanhf(x) after bias (Tanh: the TANH instantiations of the kernels only)
+  const float* mask;  // null, or the saved activation a = mask[orow*ldmask+n] of the layer below: multiply by (a > 0) (ReLU
+  int ldmask;         // backward, EPI_MASK_RELU) or by 1 - a^2 (Tanh backward, EPI_MASK_TANH)
+  int mask_mode;
   int accumulate;     // C += instead of C =   (shorthand for addend == C)
   const float* addend; // optional: C = result + addend[same row/col layout as C]
   int rowmap;
@@ -307,7 +331,7 @@ __device__ __forceinline__ void st8(T* dst, const float (&v)[8]) {
 }
 
 // ------------------------------------------------------------------------------------ gemm_nt
-template <typename T, int BN, class AL>
+template <typename T, int BN, class AL, bool TANH = false>
 __device__ __forceinline__ void nt_body(const AL& al, const T* __restrict__ Bp, int Kp, const Epi& ep, int bx, int by) {
   constexpr int BM = 128, BK = Tile<T>::BK, LD = Tile<T>::LD;
   constexpr int NT = BN / 16;
@@ -408,10 +432,13 @@ __device__ __forceinline__ void nt_body(const AL& al, const T* __restrict__ Bp, 
       for (int j = 0; j < NT; ++j) {
         const int n4 = n0 + j * 16 + ng;
         float4 v = {acc[i][j][0] + bv[j].x, acc[i][j][1] + bv[j].y, acc[i][j][2] + bv[j].z, acc[i][j][3] + bv[j].w};
-        if (ep.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        if (ep.act) {
+          v.x = epi_activate<TANH>(v.x, ep.act); v.y = epi_activate<TANH>(v.y, ep.act);
+          v.z = epi_activate<TANH>(v.z, ep.act); v.w = epi_activate<TANH>(v.w, ep.act);
+        }
         if (ep.mask != nullptr) {
-          v.x = mk[j].x > 0.f ? v.x : 0.f; v.y = mk[j].y > 0.f ? v.y : 0.f;
-          v.z = mk[j].z > 0.f ? v.z : 0.f; v.w = mk[j].w > 0.f ? v.w : 0.f;
+          v.x = epi_gate<TANH>(v.x, mk[j].x, ep.mask_mode); v.y = epi_gate<TANH>(v.y, mk[j].y, ep.mask_mode);
+          v.z = epi_gate<TANH>(v.z, mk[j].z, ep.mask_mode); v.w = epi_gate<TANH>(v.w, mk[j].w, ep.mask_mode);
         }
         if (add != nullptr) { v.x += old[j].x; v.y += old[j].y; v.z += old[j].z; v.w += old[j].w; }
         if (rok && n4 < ep.N) *reinterpret_cast<float4*>(ep.C + orow * ep.ldc + n4) = v;
@@ -426,8 +453,8 @@ __device__ __forceinline__ void nt_body(const AL& al, const T* __restrict__ Bp, 
           const bool ok = rok && n < ep.N;
           float v = acc[i][j][r];
           if (ep.bias != nullptr) v += ep.bias[n < ep.N ? n : 0];
-          if (ep.relu) v = fmaxf(v, 0.f);
-          if (ep.mask != nullptr) v = ep.mask[ok ? orow * ep.ldmask + n : 0] > 0.f ? v : 0.f;
+          if (ep.act) v = epi_activate<TANH>(v, ep.act);
+          if (ep.mask != nullptr) v = epi_gate<TANH>(v, ep.mask[ok ? orow * ep.ldmask + n : 0], ep.mask_mode);
           if (add != nullptr) v += add[ok ? orow * ep.ldc + n : 0];
           if (ok) ep.C[orow * ep.ldc + n] = v;
           else if (rok && n < ep.npad) ep.C[orow * ep.ldc + n] = 0.f;
@@ -436,9 +463,9 @@ __device__ __forceinline__ void nt_body(const AL& al, const T* __restrict__ Bp, 
   }
 }
 
-template <typename T, int BN, class AL>
+template <typename T, int BN, class AL, bool TANH = false>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(AL al, const T* __restrict__ Bp, int Kp, Epi ep) {
-  nt_body<T, BN, AL>(al, Bp, Kp, ep, blockIdx.x, blockIdx.y);
+  nt_body<T, BN, AL, TANH>(al, Bp, Kp, ep, blockIdx.x, blockIdx.y);
 }
 
 // ------------------------------------------------------------------------------------ gemm_nt, skinny M
@@ -447,7 +474,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(AL al, const T* __restrict
 // for K = 1024 (27 us). Here a block is 32 rows x 64 columns (M/32 x N/64 blocks: 128 for the NatureCNN projector), wave w
 // owns column tile w for both row tiles, the weight arrives in fragment order (PK_FRAG / PK_FRAGT: one contiguous 1 KB read per
 // fragment, straight into registers, no LDS), and EIGHT K-stages of A rows and weight fragments are in flight per thread.
-template <typename T, class AL>
+template <typename T, class AL, bool TANH = false>
 __global__ __launch_bounds__(256) void gemm_nt_deep_kernel(AL al, const T* __restrict__ Bf, int Np, int Kp, Epi ep) {
   constexpr int BM = 32, BK = Tile<T>::BK, LD = Tile<T>::LD, D = 8;
   typedef typename Frag<T>::type frag_t;
@@ -510,10 +537,14 @@ __global__ __launch_bounds__(256) void gemm_nt_deep_kernel(AL al, const T* __res
         const float4 bv = *reinterpret_cast<const float4*>(ep.bias + (n4 < ep.N ? n4 : 0));
         v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
       }
-      if (ep.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+      if (ep.act) {
+        v.x = epi_activate<TANH>(v.x, ep.act); v.y = epi_activate<TANH>(v.y, ep.act);
+        v.z = epi_activate<TANH>(v.z, ep.act); v.w = epi_activate<TANH>(v.w, ep.act);
+      }
       if (ep.mask != nullptr) {
         const float4 mk = *reinterpret_cast<const float4*>(ep.mask + (ok ? orow * ep.ldmask + n4 : 0));
-        v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f; v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
+        v.x = epi_gate<TANH>(v.x, mk.x, ep.mask_mode); v.y = epi_gate<TANH>(v.y, mk.y, ep.mask_mode);
+        v.z = epi_gate<TANH>(v.z, mk.z, ep.mask_mode); v.w = epi_gate<TANH>(v.w, mk.w, ep.mask_mode);
       }
       if (add != nullptr) {
         const float4 old = *reinterpret_cast<const float4*>(add + (ok ? orow * ep.ldc + n4 : 0));
@@ -528,8 +559,8 @@ __global__ __launch_bounds__(256) void gemm_nt_deep_kernel(AL al, const T* __res
         const bool ok = rok && n < ep.N;
         float v = acc[i][r];
         if (ep.bias != nullptr) v += ep.bias[n < ep.N ? n : 0];
-        if (ep.relu) v = fmaxf(v, 0.f);
-        if (ep.mask != nullptr) v = ep.mask[ok ? orow * ep.ldmask + n : 0] > 0.f ? v : 0.f;
+        if (ep.act) v = epi_activate<TANH>(v, ep.act);
+        if (ep.mask != nullptr) v = epi_gate<TANH>(v, ep.mask[ok ? orow * ep.ldmask + n : 0], ep.mask_mode);
         if (add != nullptr) v += add[ok ? orow * ep.ldc + n : 0];
         if (ok) ep.C[orow * ep.ldc + n] = v;
         else if (rok && n < ep.npad) ep.C[orow * ep.ldc + n] = 0.f;

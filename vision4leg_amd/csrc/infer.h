@@ -2407,8 +2407,13 @@ __global__ __launch_bounds__(1024) void rollout_cnn_kernel(const ActCtl* __restr
 // ------------------------------------------------------------------------------------------ rollout step, state MLP
 // Net / GaussianContPolicyBasicBias pair on proprioception only (networks/nets.py:16-55, starter/ppo_state.py): shared
 // base MLP (S -> 256 -> 256, ReLU) + per-net head (256 -> 256 -> 256 -> out). One sample per block, blockIdx.y = net.
+// ACT (V4L_ACT_*): the hidden activation, a compile-time choice — the ReLU instantiations are the code they were before it existed
+template <int ACT> __device__ __forceinline__ float hidden_act(float x) {
+  if constexpr (ACT == V4L_ACT_TANH) return tanhf(x);
+  else return fmaxf(x, 0.f);
+}
 struct InfMlp { const void *wf1, *wf2; const float *bf1, *bf2; int S, Sp, Kp1; };
-template <typename T>
+template <typename T, int ACT = V4L_ACT_RELU>
 __global__ __launch_bounds__(1024) void rollout_mlp_kernel(const ActCtl* __restrict__ ctlc, const float* __restrict__ obs, int E,
                                                            InfMlp w, InfCnnHeadPair hd, InfFinish fin,
                                                            float* __restrict__ state_roll) {
@@ -2425,11 +2430,12 @@ __global__ __launch_bounds__(1024) void rollout_mlp_kernel(const ActCtl* __restr
     if (net == 0 && tid < w.Sp) state_roll[((int64_t)t_step * E + b) * w.Sp + tid] = x;
   }
   __syncthreads();
-  auto relu_store = [&](T* dst, const f32x4& a, const float* bias) {
+  auto relu_store = [&](T* dst, const f32x4& a, const float* bias) {  // (bias, the hidden activation, operand-type store)
     if (fr == 0) {
       const int n4 = wave * 16 + qr;
       const float4 bb = *reinterpret_cast<const float4*>(bias + n4);
-      st4(dst + n4, fmaxf(a[0] + bb.x, 0.f), fmaxf(a[1] + bb.y, 0.f), fmaxf(a[2] + bb.z, 0.f), fmaxf(a[3] + bb.w, 0.f));
+      st4(dst + n4, hidden_act<ACT>(a[0] + bb.x), hidden_act<ACT>(a[1] + bb.y), hidden_act<ACT>(a[2] + bb.z),
+          hidden_act<ACT>(a[3] + bb.w));
     }
   };
   relu_store(hbuf[0], w.Kp1 == 128 ? gemv_tile<T, 4, 4>(sin, (const T*)w.wf1, 128, wave, lane)

@@ -198,7 +198,7 @@ struct RollMlp2Lds {
   static constexpr int LDI = 128 + 8, LDH = 256 + 8;
   static constexpr size_t bytes = (size_t)64 * LDI * 2 + (size_t)2 * 64 * LDH * 2 + (3 * 64 * 16 + 3 * 16) * 4;
 };
-template <typename H>
+template <typename H, int ACT = V4L_ACT_RELU>
 __global__ __launch_bounds__(1024) void rollout_mlp2_kernel(const float* __restrict__ obs, int E, RollMlp2 a, InfFinish fin,
                                                             float* __restrict__ state_roll) {
   constexpr int LDI = RollMlp2Lds::LDI, LDH = RollMlp2Lds::LDH;
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(1024) void rollout_mlp2_kernel(const float* __restr
   }
   if (tid < 16) b2_s[tid] = tid < a.nout[net] ? a.b2[net][tid] : 0.f;
   __syncthreads();
-  // y[:, tile] = relu(x . W^T + b) for every row tile; x rows in LDS (stride ldx), weights held in registers
+  // y[:, tile] = act(x . W^T + b) (ACT: ReLU or Tanh, csrc/infer.h hidden_act) for every row tile; x rows in LDS (stride ldx), weights held in registers
   auto layer = [&](const hx8<H>* w, auto ks_tag, const H* x, int ldx, const float4 bb, H* y) {
     constexpr int KS = decltype(ks_tag)::value;
     for (int mt = 0; mt < MT; ++mt) {
@@ -254,22 +254,33 @@ __global__ __launch_bounds__(1024) void rollout_mlp2_kernel(const float* __restr
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
         mma_k32(acc, w[ks], *reinterpret_cast<const hx8<H>*>(x + (mt * 16 + fr) * ldx + ks * 32 + g * 8));
-      st4(y + (mt * 16 + fr) * LDH + n4, fmaxf(acc[0] + bb.x, 0.f), fmaxf(acc[1] + bb.y, 0.f), fmaxf(acc[2] + bb.z, 0.f),
-          fmaxf(acc[3] + bb.w, 0.f));
+      st4(y + (mt * 16 + fr) * LDH + n4, hidden_act<ACT>(acc[0] + bb.x), hidden_act<ACT>(acc[1] + bb.y),
+          hidden_act<ACT>(acc[2] + bb.z), hidden_act<ACT>(acc[3] + bb.w));
+    }
+  };
+  // ReLU: three layers' fragments are live at a time (96 of the 128 registers a 1024-thread block leaves a lane). tanhf's
+  // temporaries do not fit beside them (it spilled one register to scratch): the Tanh instantiation requests the fourth and
+  // the last layer's fragments one layer later, two layers' live at a time
+  constexpr bool AHEAD = ACT == V4L_ACT_RELU;
+  auto load4 = [&](hx8<H> (&r)[8]) {
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) r[ks] = frag(a.w1[net], 8, wave, ks);
+  };
+  auto load5 = [&](hx8<H> (&r)[8]) {
+    if (wave < 4) {
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) r[ks] = frag(a.w2[net], 8, 0, ks);
     }
   };
   layer(r1, std::integral_constant<int, 4>(), xin, LDI, bb1, ha);
   hx8<H> r4[8], r5[8];
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks) r4[ks] = frag(a.w1[net], 8, wave, ks);
+  if constexpr (AHEAD) load4(r4);
   __syncthreads();
   layer(r2, std::integral_constant<int, 8>(), ha, LDH, bb2, hb);
-  if (wave < 4) {
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) r5[ks] = frag(a.w2[net], 8, 0, ks);
-  }
+  if constexpr (AHEAD) load5(r5); else load4(r4);
   __syncthreads();
   layer(r3, std::integral_constant<int, 8>(), hb, LDH, bb3, ha);
+  if constexpr (!AHEAD) load5(r5);
   __syncthreads();
   layer(r4, std::integral_constant<int, 8>(), ha, LDH, bb4, hb);
   __syncthreads();

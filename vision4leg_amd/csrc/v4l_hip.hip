@@ -140,20 +140,37 @@ static inline ADense dense(const float* p, int lda, int M, int K, const int* row
   a.p = p; a.lda = lda; a.M = M; a.K = K; a.rowidx = rowidx; a.tokmap = tokmap; a.mask = mask;
   return a;
 }
-static inline Epi mk_epi(float* C, int ldc, int N, const float* bias = nullptr, int relu = 0) {
+static inline Epi mk_epi(float* C, int ldc, int N, const float* bias = nullptr, int act = EPI_ACT_NONE) {
   Epi e;
   memset(&e, 0, sizeof(e));
-  e.C = C; e.ldc = ldc; e.N = N; e.bias = bias; e.relu = relu;
+  e.C = C; e.ldc = ldc; e.N = N; e.bias = bias; e.act = act;
   e.rowmap = ROWMAP_IDENT;
   return e;
 }
 
+static inline bool epi_wants_tanh(const Epi& ep) {
+  return ep.act == EPI_ACT_TANH || (ep.mask != nullptr && ep.mask_mode == EPI_MASK_TANH);
+}
 // C = epi(A * Bp^T): Bp is a packed [Np][Kp] operand (Np % 16 == 0, Kp % 64 == 0)
 template <typename T, class AL>
 static int launch_nt(hipStream_t s, const AL& al, int M, const T* Bp, int Np, int Kp, Epi ep, double flops) {
   if (M <= 0) return 0;
   ep.M = M;
   const int gx = cdiv(M, 128);
+  if (epi_wants_tanh(ep)) {  // the kernels' TANH instantiations (csrc/gemm.h epi_activate): dense layers only
+    if constexpr (std::is_same<AL, ADense>::value) {
+      if (Np % 64 == 0) {
+        V4L_KLAUNCH("gemm_nt", flops, s, (gemm_nt_kernel<T, 64, AL, true>), dim3(gx, Np / 64), dim3(256), 0, s, al, Bp, Kp, ep);
+      } else if (Np % 32 == 0) {
+        V4L_KLAUNCH("gemm_nt", flops, s, (gemm_nt_kernel<T, 32, AL, true>), dim3(gx, Np / 32), dim3(256), 0, s, al, Bp, Kp, ep);
+      } else {
+        V4L_KLAUNCH("gemm_nt", flops, s, (gemm_nt_kernel<T, 16, AL, true>), dim3(gx, Np / 16), dim3(256), 0, s, al, Bp, Kp, ep);
+      }
+      V4L_LAUNCH_CHECK();
+      return 0;
+    }
+    V4L_REQUIRE(false, "internal: a Tanh epilogue on a GEMM that is not a dense layer");
+  }
   if (Np % 64 == 0) {
     V4L_KLAUNCH("gemm_nt", flops, s, (gemm_nt_kernel<T, 64, AL>), dim3(gx, Np / 64), dim3(256), 0, s, al, Bp, Kp, ep);
   } else if (Np % 32 == 0) {
@@ -417,8 +434,12 @@ static inline bool nt_deep_shape(int M, int Kp) {
 template <typename T>
 static int launch_nt_deep(hipStream_t s, const ADense& al, const T* Bf, int Np, int Kp, Epi ep, double flops) {
   ep.M = al.M;
-  V4L_KLAUNCH("gemm_nt_deep", flops, s, (gemm_nt_deep_kernel<T, ADense>), dim3(cdiv(al.M, 32), cdiv(Np, 64)), dim3(256), 0, s, al,
-              Bf, Np, Kp, ep);
+  if (epi_wants_tanh(ep))
+    V4L_KLAUNCH("gemm_nt_deep", flops, s, (gemm_nt_deep_kernel<T, ADense, true>), dim3(cdiv(al.M, 32), cdiv(Np, 64)), dim3(256), 0, s,
+                al, Bf, Np, Kp, ep);
+  else
+    V4L_KLAUNCH("gemm_nt_deep", flops, s, (gemm_nt_deep_kernel<T, ADense>), dim3(cdiv(al.M, 32), cdiv(Np, 64)), dim3(256), 0, s, al,
+                Bf, Np, Kp, ep);
   V4L_LAUNCH_CHECK();
   return 0;
 }
@@ -506,11 +527,15 @@ static int lin_dgrad(const Ctx& c, const Lin& L, const ADense& y, Epi ep) {
   return launch_nt<T>(c.s, y, y.M, (const T*)c.net->packed + L.pkt, L.Rt, L.Ct, ep, 2.0 * y.M * L.N * L.K);
 }
 
-// forward through Linear(+ReLU) layers; outs[i] receives layer i's output
+// the net's hidden activation (cfg.activation) as the GEMM epilogue's selectors: forward side, backward side
+static inline int epi_act(const v4l_net* n) { return n->cfg.activation == V4L_ACT_TANH ? EPI_ACT_TANH : EPI_ACT_RELU; }
+static inline int epi_mask_mode(const v4l_net* n) { return n->cfg.activation == V4L_ACT_TANH ? EPI_MASK_TANH : EPI_MASK_RELU; }
+
+// forward through Linear(+activation) layers; outs[i] receives layer i's output
 template <typename T>
-static int chain_fwd(const Ctx& c, const Lin* Ls, int k, ADense in, const Act* outs, bool relu_last, bool zero_pad_last = false) {
+static int chain_fwd(const Ctx& c, const Lin* Ls, int k, ADense in, const Act* outs, bool act_last, bool zero_pad_last = false) {
   for (int i = 0; i < k; ++i) {
-    Epi ep = mk_epi(outs[i].p, outs[i].ld, Ls[i].N, nullptr, (i < k - 1 || relu_last) ? 1 : 0);
+    Epi ep = mk_epi(outs[i].p, outs[i].ld, Ls[i].N, nullptr, (i < k - 1 || act_last) ? epi_act(c.net) : EPI_ACT_NONE);
     // the last layer of a head stack writes out_dim of its row's OUT_LD columns: the rest as zeros from the same epilogue
     // (its column tiles cover Np >= 16 = OUT_LD columns) instead of a memset launch ahead of the chain
     if (i == k - 1 && zero_pad_last && outs[i].ld <= Ls[i].Np) ep.npad = outs[i].ld;
@@ -535,6 +560,7 @@ static int chain_bwd(Ctx& c, const Lin* Ls, int k, const ADense& in, const Act* 
       Epi ep = mk_epi(dbufs[i - 1], acts[i - 1].w, acts[i - 1].w);
       ep.mask = acts[i - 1].p;
       ep.ldmask = acts[i - 1].ld;
+      ep.mask_mode = epi_mask_mode(c.net);
       if ((rc = lin_dgrad<T>(c, Ls[i], y, ep))) return rc;
       y = dense(dbufs[i - 1], acts[i - 1].w, y.M, acts[i - 1].w);
     } else if (din != nullptr) {
@@ -827,6 +853,11 @@ int v4l_net::build() {
   const v4l_net_cfg& c = cfg;
   V4L_REQUIRE(c.kind >= V4L_NET_MLP && c.kind <= V4L_NET_LOCO_VIS, "v4l_net_create: unknown net kind %d", c.kind);
   V4L_REQUIRE(c.compute == V4L_F32 || c.compute == V4L_BF16 || c.compute == V4L_F16, "v4l_net_create: unknown compute mode %d", c.compute);
+  V4L_REQUIRE(c.activation == V4L_ACT_RELU || c.activation == V4L_ACT_TANH,
+              "v4l_net_create: unknown activation %d (V4L_ACT_RELU 0 | V4L_ACT_TANH 1)", c.activation);
+  V4L_REQUIRE(c.activation == V4L_ACT_RELU || c.kind == V4L_NET_MLP,
+              "v4l_net_create: activation V4L_ACT_TANH runs on net kind V4L_NET_MLP only (got kind %d); the kinds V4L_NET_CNN, "
+              "V4L_NET_LOCO, V4L_NET_CNN_VIS and V4L_NET_LOCO_VIS take V4L_ACT_RELU", c.kind);
   V4L_REQUIRE(c.out_dim > 0 && c.out_dim <= V4L_MAX_ACT, "v4l_net_create: 1<=out_dim<=%d (V4L_MAX_ACT) required, got %d", V4L_MAX_ACT,
               c.out_dim);
   if (vis_only())  // vision-only nets have no proprio branch: the observation row is the depth stack alone
@@ -1736,12 +1767,14 @@ int v4l_net::backward_t(const float* state, const T* image, const int* rowidx, i
   };
 
   if (c.kind == V4L_NET_MLP) {
-    // head stack, then the base MLP; the grad w.r.t. the base output (ReLU-masked) is handed over in `hand`
+    // head stack, then the base MLP; the grad w.r.t. the base output (through its activation: ReLU mask or 1 - a^2) is handed
+    // over in `hand`
     const Act& last = eacts[ne - 1];
     float* hand = ws + L.dhc;
     Epi din = mk_epi(hand, last.w, last.w);
     din.mask = last.p;
     din.ldmask = last.ld;
+    din.mask_mode = epi_mask_mode(this);
     if ((rc = chain_bwd<T>(cx, head.data(), nh + 1, dense(last.p, last.ld, n, last.w), hacts, dy, dhhp, &din))) return rc;
     if ((rc = chain_bwd<T>(cx, enc.data(), ne, sin, eacts, dense(hand, last.w, n, last.w), dehp, nullptr))) return rc;
     return wgrad_finish<T>(cx);
@@ -2414,11 +2447,11 @@ static int run_actor_dense_cnn(v4l_actor* a, const StepIO& io, hipStream_t s) {
 }
 
 // state-only MLP nets, bf16: one launch per env step, one block per net for ALL E rows (csrc/rollout_dense.h rollout_mlp2_kernel)
-template <typename H>
+template <typename H, int ACT>
 static int run_actor_mlp2(v4l_actor* a, const StepIO& io, hipStream_t s) {
   v4l_net *pf = a->pf, *vf = a->vf;
   const int E = a->E;
-  V4L_HIP_CHECK(lds_limit<&rollout_mlp2_kernel<H>>(RollMlp2Lds::bytes));
+  V4L_HIP_CHECK((lds_limit<&rollout_mlp2_kernel<H, ACT>>(RollMlp2Lds::bytes)));
   const H* pk = (const H*)pf->packed;
   const H* vk = (const H*)vf->packed;
   const Layout Lp = pf->layout(E), Lv = vf->layout(E);
@@ -2437,14 +2470,14 @@ static int run_actor_mlp2(v4l_actor* a, const StepIO& io, hipStream_t s) {
   head(1, vf, vk, a->ws + Lp.total + Lv.out);
   const InfFinish fin = step_finish(a, io, s);
   g_op = "step";
-  V4L_KLAUNCH("rollout_mlp", 2.0 * 2 * E * (128.0 * 256 + 4 * 256 * 256), s, rollout_mlp2_kernel<H>, dim3(2), dim3(1024),
+  V4L_KLAUNCH("rollout_mlp", 2.0 * 2 * E * (128.0 * 256 + 4 * 256 * 256), s, (rollout_mlp2_kernel<H, ACT>), dim3(2), dim3(1024),
               RollMlp2Lds::bytes, s, io.obs, E, m, fin, io.state_roll);
   V4L_LAUNCH_CHECK();
   return 0;
 }
 
 // state-only MLP nets of the shipped shape: one launch per env step (rollout_mlp_kernel)
-template <typename T>
+template <typename T, int ACT>
 static int run_actor_fused_mlp(v4l_actor* a, const StepIO& io, hipStream_t s) {
   v4l_net *pf = a->pf, *vf = a->vf;
   const int E = a->E;
@@ -2468,7 +2501,7 @@ static int run_actor_fused_mlp(v4l_actor* a, const StepIO& io, hipStream_t s) {
   head(hd.n[1], vf, vk, ws_vf + Lv.out);
   const InfFinish fin = step_finish(a, io, s);
   g_op = "step";
-  V4L_KLAUNCH("rollout_mlp", 2.0 * 2 * E * (128.0 * 256 + 4 * 256 * 256), s, rollout_mlp_kernel<T>, dim3(E, 2), dim3(1024), 0, s,
+  V4L_KLAUNCH("rollout_mlp", 2.0 * 2 * E * (128.0 * 256 + 4 * 256 * 256), s, (rollout_mlp_kernel<T, ACT>), dim3(E, 2), dim3(1024), 0, s,
               (const ActCtl*)a->ctl, io.obs, E, en, hd, fin, io.state_roll);
   V4L_LAUNCH_CHECK();
   return 0;
@@ -2601,7 +2634,7 @@ static int launch_actor_loss(hipStream_t s, const ActorArgs& aa, dim3 blk) {
 extern "C" {
 
 const char* v4l_last_error(void) { return v4l::last_error(); }
-int v4l_version(void) { return 107; }  // per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
+int v4l_version(void) { return 108; }  // v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
 int v4l_abi_sizeof(int which) {
   return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) : -1;
 }
@@ -2962,8 +2995,8 @@ int v4l_actor_create(v4l_net* pf, v4l_net* vf, int E, v4l_actor** out) {
   V4L_REQUIRE(pf && vf && out && E > 0, "v4l_actor_create: bad argument");
   V4L_REQUIRE(pf->cfg.has_logstd && vf->cfg.out_dim == 1 && pf->cfg.kind == vf->cfg.kind &&
                   pf->cfg.compute == vf->cfg.compute && pf->cfg.state_dim == vf->cfg.state_dim &&
-                  pf->cfg.n_enc_hidden == vf->cfg.n_enc_hidden,
-              "v4l_actor_create: pf must be a Gaussian policy and vf a value net of the same kind/compute/shape");
+                  pf->cfg.n_enc_hidden == vf->cfg.n_enc_hidden && pf->cfg.activation == vf->cfg.activation,
+              "v4l_actor_create: pf must be a Gaussian policy and vf a value net of the same kind/compute/shape/activation");
   v4l_actor* a = new v4l_actor();
   a->pf = pf; a->vf = vf; a->E = E;
   *out = a;
@@ -3041,10 +3074,18 @@ static int run_actor_step(v4l_actor* a, const StepIO& io, int shared_encoder, hi
   V4L_REQUIRE(pf->bound && vf->bound, "v4l_actor_step: nets are not bound");
   const int compute = pf->cfg.compute;
   switch (const StepRoute route = step_route(a, shared_encoder)) {
+    // (the state-MLP kernels carry the hidden activation as a template argument; v4l_actor_create saw pf's and vf's agree)
     case StepRoute::MLP_ONE_BLOCK:
-      return by_half(compute, [&](auto tag) -> int { return run_actor_mlp2<typename decltype(tag)::type>(a, io, s); });
+      return by_half(compute, [&](auto tag) -> int {
+        typedef typename decltype(tag)::type H;
+        return pf->cfg.activation == V4L_ACT_TANH ? run_actor_mlp2<H, V4L_ACT_TANH>(a, io, s) : run_actor_mlp2<H, V4L_ACT_RELU>(a, io, s);
+      });
     case StepRoute::MLP_PER_SAMPLE:
-      return by_compute(compute, [&](auto tag) -> int { return run_actor_fused_mlp<typename decltype(tag)::type>(a, io, s); });
+      return by_compute(compute, [&](auto tag) -> int {
+        typedef typename decltype(tag)::type T;
+        return pf->cfg.activation == V4L_ACT_TANH ? run_actor_fused_mlp<T, V4L_ACT_TANH>(a, io, s)
+                                                  : run_actor_fused_mlp<T, V4L_ACT_RELU>(a, io, s);
+      });
     case StepRoute::CNN_DENSE:
       return by_half(compute, [&](auto tag) -> int { return run_actor_dense_cnn<typename decltype(tag)::type>(a, io, s); });
     case StepRoute::CNN_PER_SAMPLE:
@@ -3242,8 +3283,9 @@ int v4l_trainer_create(v4l_net* pf, v4l_net* vf, v4l_net* target_pf, v4l_trainer
               "v4l_trainer_create: pf/target_pf must be Gaussian policies and vf a scalar value net");
   V4L_REQUIRE(pf->cfg.compute == vf->cfg.compute && pf->cfg.compute == target_pf->cfg.compute &&
                   pf->cfg.kind == vf->cfg.kind && pf->cfg.kind == target_pf->cfg.kind &&
-                  pf->cfg.state_dim == vf->cfg.state_dim && pf->total_params == target_pf->total_params,
-              "v4l_trainer_create: pf, vf and target_pf disagree on kind/compute/shape");
+                  pf->cfg.state_dim == vf->cfg.state_dim && pf->total_params == target_pf->total_params &&
+                  pf->cfg.activation == vf->cfg.activation && pf->cfg.activation == target_pf->cfg.activation,
+              "v4l_trainer_create: pf, vf and target_pf disagree on kind/compute/shape/activation");
   v4l_trainer* t = new v4l_trainer();
   t->pf = pf; t->vf = vf; t->tpf = target_pf;
   *out = t;

@@ -19,13 +19,18 @@ def obs_dim(case):
 
 
 def build_nets(networks, policies, case):
-    """pf / vf exactly as the starters wire them (shared encoder / base). case: kind in {loco, cnn, mlp, loco_vis, cnn_vis},
+    """pf / vf exactly as the starters wire them (shared encoder / base). case: kind in {loco, cnn, mlp, loco_vis, cnn_vis}
+    plus suffixes (_tn / _pe / _max, then _tact, then _tanh),
     S, A, enc (encoder hidden_shapes), head (append_hidden_shapes) and, per kind, layers / ff / visual_dim."""
     S, A, kind = case["S"], case["A"], case["kind"]
     net = {"append_hidden_shapes": list(case["head"]), "base_type": networks.MLPBase}
     pol = {}
     if kind.endswith("_tanh"):  # the same nets with a TanhNormal policy head (tanh_action=True, continuous_policy.py:85-146)
         pol["tanh_action"] = True
+        kind = kind[:-5]
+    if kind.endswith("_tact"):  # the same nets with Tanh activations (activation_func=nn.Tanh, the starters' commented switch)
+        import torch.nn as nn
+        net["activation_func"] = nn.Tanh
         kind = kind[:-5]
     if kind in ("loco_max", "loco_vis_max"):  # the same nets with max_pool=True (nets.py:1022-1030, 884-889)
         net["max_pool"] = True

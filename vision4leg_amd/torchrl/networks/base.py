@@ -48,7 +48,8 @@ class Flatten(nn.Module):
 
 
 class MLPBase(_Container):
-    """Linear+ReLU stack; `seq_fcs.{0,2,...}` (reference base.py:8-44). Only ReLU / no LayerNorm runs on HIP."""
+    """Linear+activation stack; `seq_fcs.{0,2,...}` (reference base.py:8-44). ReLU and — under networks.Net — Tanh run on
+    HIP, without LayerNorm."""
 
     def __init__(self, input_shape, hidden_shapes, activation_func=nn.ReLU, init_func=init.basic_init,
                  add_ln=False, last_activation_func=None):
@@ -76,8 +77,10 @@ class MLPBase(_Container):
         self.seq_fcs = nn.Sequential(*mods)
 
     def hip_supported(self):
-        return (self.activation_func is nn.ReLU and self.last_activation_func is nn.ReLU and not self.add_ln
-                and len(self.hidden_shapes) >= 1)
+        """ReLU or Tanh throughout (a last activation of its own stays refused), no LayerNorm. Which of the two a net kind
+        takes is the top-level net's check (nets.py: Tanh runs on networks.Net only)."""
+        return (self.activation_func in (nn.ReLU, nn.Tanh) and self.last_activation_func is self.activation_func
+                and not self.add_ln and len(self.hidden_shapes) >= 1)
 
 
 class NatureEncoder(_Container):

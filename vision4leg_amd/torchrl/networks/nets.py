@@ -27,9 +27,22 @@ def _fill_hidden(dst, values, what):
     return len(values)
 
 
+_ACTIVATIONS = {nn.ReLU: _lib.V4L_ACT_RELU, nn.Tanh: _lib.V4L_ACT_TANH}
+
+
 def _check_relu(module, what):
-    if module.activation_func is not nn.ReLU or getattr(module, "add_ln", False):
+    if getattr(module, "add_ln", False):
+        raise NotImplementedError("vision4leg_amd: %s: add_ln=True (LayerNorm after the hidden activations) does not run on "
+                                  "the HIP engine" % what)
+    if module.activation_func is nn.Tanh:
+        raise NotImplementedError("vision4leg_amd: %s: activation_func=nn.Tanh runs on networks.Net (the state-MLP net) only; "
+                                  "this net takes nn.ReLU" % what)
+    if module.activation_func is not nn.ReLU:
         raise NotImplementedError("vision4leg_amd: %s: only ReLU without LayerNorm runs on the HIP engine" % what)
+    base = getattr(getattr(module, "encoder", None), "base", None)
+    if base is not None and base.activation_func is nn.Tanh:
+        raise NotImplementedError("vision4leg_amd: %s: a Tanh encoder MLP runs under networks.Net only; this net takes "
+                                  "nn.ReLU" % what)
 
 
 class _HipNetMixin:
@@ -118,11 +131,14 @@ class Net(_HipNetMixin, nn.Module):
         self.seq_append_fcs = nn.Sequential(*self.append_fcs)
 
     def _net_cfg(self):
-        _check_relu(self, "Net")
-        if not self.base.hip_supported():
-            raise NotImplementedError("vision4leg_amd: Net.base must be an MLPBase with ReLU activations")
+        if self.add_ln or self.activation_func not in _ACTIVATIONS:
+            raise NotImplementedError("vision4leg_amd: Net: only ReLU or Tanh without LayerNorm runs on the HIP engine")
+        if not self.base.hip_supported() or self.base.activation_func is not self.activation_func:
+            raise NotImplementedError("vision4leg_amd: Net.base must be an MLPBase with the net's activation (ReLU or Tanh) "
+                                      "throughout: a last_activation_func of its own does not run on the HIP engine")
         c = _lib.NetCfg()
         c.kind = _lib.V4L_NET_MLP
+        c.activation = _ACTIVATIONS[self.activation_func]  # (reference base.py:13,33,40, nets.py:24,41-44)
         c.compute = default_compute()
         c.state_dim = self.base.input_dim
         c.out_dim = self.output_dim
