@@ -309,6 +309,15 @@ typedef struct v4l_ppo_hyper {
   float beta1, beta2, eps; /* Adam: 0.9, 0.999, 1e-5 (a2c.py:30-40) */
   int clipped_value_loss;  /* ppo.py:105-112 */
   int world_size;       /* data-parallel ranks; losses are scaled by 1/(n*world_size) */
+  /* (version 109) weight decay of both optimisers, torch/optim/adam.py::_single_tensor_adam: 0 = none. decoupled_weight_decay
+   * 0 = torch.optim.Adam(weight_decay=wd), L2: `grad = grad.add(param, alpha=weight_decay)` (adam.py:429) on the gradient
+   * clip_grad_norm_ already scaled, so the logged norms never hold a decay term; != 0 = torch.optim.AdamW:
+   * `param.mul_(1 - lr * weight_decay)` (adam.py:419) with the learning rate of that optimiser and that update, then the
+   * unchanged Adam step. One param group: every tensor decays, biases and log sigma included; a shared encoder tensor decays in
+   * the critic's step and again in the actor's. A skipped step (v4l_trainer_begin_guarded) applies no decay. A zeroed tail is
+   * plain Adam. Must be finite and >= 0; fixed for the life of a trainer (the captured graphs bake the kernel variant in). */
+  double weight_decay;          /* a double, as torch holds it: the decoupled factor is formed from it in double */
+  int decoupled_weight_decay;
 } v4l_ppo_hyper;
 
 typedef struct v4l_rollout {

@@ -47,6 +47,7 @@ class PPOHyper(C.Structure):
     ("clip_para", C.c_float), ("entropy_coeff", C.c_float), ("max_grad_norm", C.c_float),
     ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
     ("clipped_value_loss", C.c_int), ("world_size", C.c_int),
+    ("weight_decay", C.c_double), ("decoupled_weight_decay", C.c_int),
   ]
 
 

@@ -846,11 +846,16 @@ struct UpdCtl {
   float beta1, beta2;
   float step_size[2];   // lr / (1 - beta1^(step+1)) for [0] pf, [1] vf — refreshed by upd_begin_body (block 0 of begin_pack_kernel)
   float bc2_sqrt[2];    // sqrt(1 - beta2^(step+1)), per optimiser
+  double weight_decay;  // v4l_ppo_hyper.weight_decay (0: plain Adam), fixed for a run of updates
+  float wd32;           // the same as torch hands it to grad.add(param, alpha=weight_decay) on fp32 tensors
+  int decoupled;        // != 0: AdamW (decay the parameter), 0: L2 (decay joins the gradient)
+  float decay[2];       // decoupled: 1 - lr * weight_decay per optimiser, formed in double and rounded once like step_size
 };
 static_assert(sizeof(UpdCtl) <= 256, "UpdCtl must fit in front of stats_cur (control buffer layout [UpdCtl | stats_cur | rowidx_cur])");
 __global__ void ctl_set_kernel(UpdCtl* c, int upd_index, long long step_pf, long long step_vf, double lr_pf, double lr_vf, float b1,
-                               float b2) {
+                               float b2, double weight_decay, int decoupled) {
   c->upd_index = upd_index; c->step[0] = step_pf; c->step[1] = step_vf; c->lr_pf = lr_pf; c->lr_vf = lr_vf; c->beta1 = b1; c->beta2 = b2;
+  c->weight_decay = weight_decay; c->wd32 = (float)weight_decay; c->decoupled = decoupled; c->decay[0] = 1.f; c->decay[1] = 1.f;
 }
 // the candidate Adam step sizes / bias corrections of the update being opened, from the committed counts + 1 (double precision,
 // like torch/optim/adam.py::_single_tensor_adam). Nothing is committed here: block 0 of each optimiser's clip_adam_kernel
@@ -869,6 +874,11 @@ __device__ __forceinline__ void upd_begin_step(UpdCtl* c) {
     } else {
       c->step_size[1] = (float)(c->lr_vf / (1.0 - pow(b1, (double)s1)));
       c->bc2_sqrt[1] = (float)sqrt(1.0 - pow(b2, (double)s1));
+    }
+    if (c->decoupled) {  // AdamW: param.mul_(1 - lr * weight_decay) with this update's learning rates (adam.py:419)
+      const double wd = c->weight_decay;
+      c->decay[0] = (float)(1.0 - c->lr_pf * wd);
+      c->decay[1] = (float)(1.0 - c->lr_vf * wd);
     }
   }
 }
@@ -910,6 +920,13 @@ __device__ __forceinline__ void upd_begin_body(UpdCtl* c, const int* __restrict_
   }
   upd_begin_step(c);
 }
+// WD: how v4l_ppo_hyper.weight_decay enters (a template argument: without decay the launch is the kernel it always was).
+//   WD_NONE       no decay
+//   WD_COUPLED    torch.optim.Adam(weight_decay=wd): grad = grad.add(param, alpha=wd) on the clipped gradient, before both moments
+//   WD_DECOUPLED  torch.optim.AdamW: param.mul_(1 - lr * wd), then the plain step on the decayed parameter
+// The norm (and the logged grad_norm) is the raw gradient's either way: clip_grad_norm_ runs before optimizer.step().
+enum { WD_NONE = 0, WD_COUPLED = 1, WD_DECOUPLED = 2 };
+template <int WD>
 __global__ __launch_bounds__(256) void clip_adam_kernel(const ParamSeg* __restrict__ segs, int nseg,
                                                         const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, const float* __restrict__ part, int npart,
@@ -920,6 +937,7 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const ParamSeg* __restri
   const ParamSeg sg = segs[find_desc(segs, nseg, (int64_t)blockIdx.x)];
   const float beta1 = ctl->beta1, beta2 = ctl->beta2;
   const float step_size = ctl->step_size[which], bc2_sqrt = ctl->bc2_sqrt[which];
+  const float wd = WD == WD_COUPLED ? ctl->wd32 : WD == WD_DECOUPLED ? ctl->decay[which] : 0.f;  // (no load for WD_NONE)
   const int lane_ = threadIdx.x & 63;
   // this thread's element: its four operands are requested before the norm is summed (they do not depend on it; behind the
   // barrier below they would be one more round trip at the end of the block's chain — round 5)
@@ -973,12 +991,15 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const ParamSeg* __restri
     if (threadIdx.x == 0) close_ctl->upd_index = u + 1;
   }
   if (!mine || skip) return;
-  const float gr = g_in * coef;
+  float gr = g_in * coef;
+  float pp = p_in;
+  if (WD == WD_COUPLED) gr = fmaf(wd, pp, gr);  // one rounding for clip_coef * g + wd * p's sum
+  if (WD == WD_DECOUPLED) pp = pp * wd;
   float mm = m_in, vv = v_in;
   mm = mm + (gr - mm) * (1.f - beta1);           // exp_avg.lerp_(grad, 1 - beta1)
   vv = vv * beta2 + (1.f - beta2) * (gr * gr);   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
   const float denom = sqrtf(vv) / bc2_sqrt + eps;
-  sg.p[i] = p_in - step_size * (mm / denom);     // param.addcdiv_(exp_avg, denom, value=-step_size)
+  sg.p[i] = pp - step_size * (mm / denom);       // param.addcdiv_(exp_avg, denom, value=-step_size)
   m[o] = mm;
   v[o] = vv;
 }

@@ -2634,7 +2634,7 @@ static int launch_actor_loss(hipStream_t s, const ActorArgs& aa, dim3 blk) {
 extern "C" {
 
 const char* v4l_last_error(void) { return v4l::last_error(); }
-int v4l_version(void) { return 108; }  // v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
+int v4l_version(void) { return 109; }  // v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
 int v4l_abi_sizeof(int which) {
   return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) : -1;
 }
@@ -3340,16 +3340,25 @@ int v4l_trainer_bind(v4l_trainer* tr, float* g_pf_dev, float* m_pf_dev, float* v
   return 0;
 }
 
+// The optimiser fields every entry point that takes a v4l_ppo_hyper checks (they are fixed for the life of a trainer: the
+// opening launch copies them into UpdCtl and the captured graphs bake the kernel variant in).
+static int check_hyper(const v4l_ppo_hyper* hp) {
+  V4L_REQUIRE(hp->weight_decay >= 0.0 && hp->weight_decay <= 3.0e38,
+              "v4l_ppo_hyper.weight_decay must be finite and >= 0 (got %g)", hp->weight_decay);
+  return 0;
+}
+
 int v4l_trainer_begin_guarded(v4l_trainer* tr, const int* rowidx_all_dev, float* stats_all_dev, int* skip_all_dev, double lr_pf,
                               double lr_vf, int64_t step_pf, int64_t step_vf, const v4l_ppo_hyper* hp, void* stream) {
   V4L_REQUIRE(tr && tr->bound && hp && step_pf >= 0 && step_vf >= 0, "v4l_trainer_begin: bad argument");
+  if (int rc = check_hyper(hp)) return rc;
   // baked into the graph (the flag pointer also decides whether the guard is on)
   if (rowidx_all_dev != tr->rowidx_all || stats_all_dev != tr->stats_all || skip_all_dev != tr->skip_all) drop_graph(tr);
   tr->rowidx_all = rowidx_all_dev;
   tr->stats_all = stats_all_dev;
   tr->skip_all = skip_all_dev;
   hipLaunchKernelGGL(ctl_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, tr->ctl, 0, (long long)step_pf, (long long)step_vf,
-                     lr_pf, lr_vf, hp->beta1, hp->beta2);
+                     lr_pf, lr_vf, hp->beta1, hp->beta2, hp->weight_decay, hp->decoupled_weight_decay != 0 ? 1 : 0);
   V4L_LAUNCH_CHECK();
   return 0;
 }
@@ -3389,6 +3398,7 @@ static int check_update_args(const v4l_trainer* tr, const v4l_rollout* ro, int n
   V4L_REQUIRE(tr->pf->cfg.kind == V4L_NET_MLP || ro->image_dev, "v4l_trainer: rollout image array missing");
   V4L_REQUIRE(!hp->clipped_value_loss || ro->values_dev, "v4l_trainer: clipped_value_loss needs values_dev");
   V4L_REQUIRE(hp->world_size >= 1, "v4l_trainer: world_size must be >= 1");
+  if (int rc = check_hyper(hp)) return rc;
   V4L_REQUIRE(tr->comm == nullptr || hp->world_size == tr->comm_world,
               "v4l_trainer: hyper.world_size (%d) differs from the communicator's (%d)", hp->world_size, tr->comm_world);
   V4L_REQUIRE(v4l_trainer_ws_floats(tr, n) <= tr->ws_floats, "v4l_trainer: workspace too small for n=%d", n);
@@ -3472,6 +3482,7 @@ static int adam_step(v4l_trainer* tr, v4l_net* net, float* g, float* m, float* v
   const float* part = tr->norm_part + which * GRAD_NORM_PARTS;
   const float* extra = nullptr;
   int nextra = 0;
+  if (int rc = check_hyper(hp)) return rc;
   g_op = "optim";
   // The gradient's sum of squares: on one GPU the backward's wgrad_reduce launch already left it, one partial per block
   // (plus log sigma's gradient, which the loss kernel writes itself); after an all-reduce the buffer is summed again.
@@ -3491,9 +3502,15 @@ static int adam_step(v4l_trainer* tr, v4l_net* net, float* g, float* m, float* v
   }
   // (a 1-dimensional policy logs log_std/std = NaN, as the reference's log_std.std() does: not a non-finite update)
   const unsigned nf_exempt = tr->pf->cfg.out_dim == 1 ? 1u << ST_LS_STD : 0u;
-  V4L_KLAUNCH("clip_adam", 0, s, clip_adam_kernel, dim3((unsigned)net->seg_blocks), dim3(256), 0, s, net->d_segs,
-              (int)net->params.size(), g, m, v, part, gb, extra, nextra, hp->max_grad_norm, hp->eps, tr->ctl, which, norm_out,
-              close_update ? tr->ctl : (UpdCtl*)nullptr, (const float*)tr->stats_cur, tr->stats_all, tr->skip_all, nf_exempt);
+  // weight_decay == 0 (with either class) is the kernel without decay: today's arithmetic, bit for bit
+#define V4L_CLIP_ADAM(WD_)                                                                                                     \
+  V4L_KLAUNCH("clip_adam", 0, s, clip_adam_kernel<WD_>, dim3((unsigned)net->seg_blocks), dim3(256), 0, s, net->d_segs,         \
+              (int)net->params.size(), g, m, v, part, gb, extra, nextra, hp->max_grad_norm, hp->eps, tr->ctl, which, norm_out, \
+              close_update ? tr->ctl : (UpdCtl*)nullptr, (const float*)tr->stats_cur, tr->stats_all, tr->skip_all, nf_exempt)
+  if (!(hp->weight_decay > 0.0)) V4L_CLIP_ADAM(WD_NONE);
+  else if (hp->decoupled_weight_decay) V4L_CLIP_ADAM(WD_DECOUPLED);
+  else V4L_CLIP_ADAM(WD_COUPLED);
+#undef V4L_CLIP_ADAM
   V4L_LAUNCH_CHECK();
   return 0;
 }
@@ -3759,7 +3776,7 @@ int v4l_trainer_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const
   // the captured launch sequence is specific to (rollout pointers, n, hyper-parameters)
   GraphKey key;
   memset(&key, 0, sizeof(key));
-  key.ro = *ro; key.hp = *hp; key.n = n;
+  key.ro = *ro; memcpy(&key.hp, hp, sizeof(*hp)); key.n = n;  // (bytewise: v4l_ppo_hyper ends in padding)
   key.gen[0] = tr->pf->gen; key.gen[1] = tr->vf->gen; key.gen[2] = tr->tpf->gen;
   if (memcmp(&key, &tr->gkey, sizeof(key)) != 0) { drop_graph(tr); tr->gkey = key; }
   if (!tr->warm) {  // first update of a configuration runs eagerly: it uploads the descriptor tables
@@ -3793,7 +3810,7 @@ int v4l_trainer_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const 
   hipStream_t s = (hipStream_t)stream;
   GraphKey key;
   memset(&key, 0, sizeof(key));
-  key.ro = *ro; key.hp = *hp; key.n = n;
+  key.ro = *ro; memcpy(&key.hp, hp, sizeof(*hp)); key.n = n;  // (bytewise: v4l_ppo_hyper ends in padding)
   key.gen[0] = tr->pf->gen; key.gen[1] = tr->vf->gen; key.gen[2] = tr->tpf->gen;
   const bool same = memcmp(&key, &tr->gkey, sizeof(key)) == 0;
   if (!use_graph || g_prof || s == nullptr || !same || !tr->warm) {

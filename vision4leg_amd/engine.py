@@ -350,7 +350,11 @@ class HipTrainer:
   torchrl/algo/on_policy/ppo.py:125-153."""
 
   def __init__(self, pf_net, vf_net, tpf_net, batch, clip_para, entropy_coeff, max_grad_norm=0.5,
-               betas=(0.9, 0.999), eps=1e-5, clipped_value_loss=False, world_size=1):
+               betas=(0.9, 0.999), eps=1e-5, clipped_value_loss=False, world_size=1, weight_decay=0.0, decoupled=False):
+    # weight_decay / decoupled: torch.optim.Adam(weight_decay=...) (L2, decoupled=False) or torch.optim.AdamW (decoupled=True) for
+    # both optimisers; fixed for the life of the trainer, like betas and eps (the captured graphs bake them in)
+    if not (float(weight_decay) >= 0.0 and float(weight_decay) != float("inf")):
+      raise ValueError("vision4leg_amd: weight_decay must be finite and >= 0 (got %r)" % (weight_decay,))
     self.pf, self.vf, self.tpf = pf_net, vf_net, tpf_net
     self.L = _lib.lib()
     for net in (pf_net, vf_net, tpf_net):
@@ -371,7 +375,7 @@ class HipTrainer:
     self.stream = torch.cuda.Stream(device=dev)  # hipGraph capture needs a non-default stream
     self._alloc_ws(batch)
     self.hp = PPOHyper(clip_para, entropy_coeff, max_grad_norm, betas[0], betas[1], eps,
-                       int(bool(clipped_value_loss)), int(world_size))
+                       int(bool(clipped_value_loss)), int(world_size), float(weight_decay), int(bool(decoupled)))
     self.step = 0  # minibatch updates run (== both Adam step counts while no guarded step was skipped)
     self._adam_steps = (0, 0)  # committed Adam step counts (pf, vf) as last known on the host
     self._guarded = False  # the open run skips non-finite optimiser steps (begin(..., skip_all=...))

@@ -25,6 +25,7 @@ import torch
 from .. import utils as atu
 from ... import replay_buffers as rb
 from .... import _lib
+from .... import optim as hip_optim
 from .... import train_state as ts
 from ....engine import HipTrainer
 
@@ -32,10 +33,13 @@ from ....engine import HipTrainer
 class _HipAdam:
     """Optimiser facade: the Adam state lives in the trainer's flat device buffers; this object carries the learning rate so
     `update_linear_schedule` and user code can read/write `param_groups[0]['lr']`, and — once PPO has attached the trainer —
-    reads and writes that state in `torch.optim.Adam`'s own `state_dict()` format (vision4leg_amd/train_state.py)."""
+    reads and writes that state in `torch.optim.Adam`'s own `state_dict()` format (vision4leg_amd/train_state.py). The other
+    group values (betas, eps, weight_decay, decoupled_weight_decay) are what PPO resolved from `optimizer_class` and handed to the
+    trainer: they are fixed, and a state written under other values does not load."""
 
-    def __init__(self, params, lr, eps=1e-5, betas=(0.9, 0.999)):
-        self.param_groups = [{"params": list(params), "lr": lr, "eps": eps, "betas": betas, "weight_decay": 0}]
+    def __init__(self, params, lr, eps=1e-5, betas=(0.9, 0.999), weight_decay=0, decoupled_weight_decay=False):
+        self.param_groups = [{"params": list(params), "lr": lr, "eps": eps, "betas": betas, "weight_decay": weight_decay,
+                              "decoupled_weight_decay": bool(decoupled_weight_decay)}]
         self._trainer = None
 
     @property
@@ -56,22 +60,29 @@ class _HipAdam:
         return net, ts.param_slices(net, self._module)
 
     def state_dict(self):
-        """What `torch.optim.Adam(net.parameters(), lr=..., eps=1e-5).state_dict()` would hold after the same steps."""
+        """What `optimizer_class(net.parameters(), lr=..., eps=1e-5).state_dict()` would hold after the same steps."""
         _, slices = self._slices()
         state = self._trainer.adam_state()
         g = self.param_groups[0]
-        return ts.export_adam(slices, state[2 * self._side], state[2 * self._side + 1], state[4][self._side], g["lr"], g["betas"], g["eps"])
+        return ts.export_adam(slices, state[2 * self._side], state[2 * self._side + 1], state[4][self._side], g["lr"], g["betas"], g["eps"],
+                              g["weight_decay"], g["decoupled_weight_decay"])
+
+    def check_group(self, group):
+        """Raise ValueError, naming both sides, for a param group written under other betas / eps / weight decay than this
+        optimiser runs (they are baked into the trainer)."""
+        g = self.param_groups[0]
+        bad = hip_optim.group_mismatch(group, g["betas"], g["eps"], g["weight_decay"], g["decoupled_weight_decay"])
+        if bad:
+            raise ValueError("vision4leg_amd: " + bad)
 
     def load_state_dict(self, sd):
-        """From this class or from a real `torch.optim.Adam` over the same module. Moments go into the trainer's buffers in
-        place, the step count to the host side (the next begin() hands it to the device), `lr` into the param group."""
+        """From this class or from a real `torch.optim.Adam` / `AdamW` over the same module. Moments go into the trainer's buffers
+        in place, the step count to the host side (the next begin() hands it to the device), `lr` into the param group. A state
+        written with other betas, eps, weight_decay or the other kind of decay raises (ValueError) before anything is written."""
         net, slices = self._slices()
         m, v, step, group = ts.import_adam(slices, sd, net.total_params)
+        self.check_group(group)
         g = self.param_groups[0]
-        if "betas" in group and tuple(float(b) for b in group["betas"]) != tuple(float(b) for b in g["betas"]) \
-                or "eps" in group and float(group["eps"]) != float(g["eps"]):
-            raise ValueError("vision4leg_amd: the optimiser state was written with betas %s / eps %s, the HIP engine runs %s / %s"
-                             % (group.get("betas"), group.get("eps"), g["betas"], g["eps"]))
         if self._side:
             self._trainer.load_adam_state(m_vf=m, v_vf=v, steps=(None, step))
         else:
@@ -180,9 +191,10 @@ class PPO:
                  opt_epochs=10, clipped_value_loss=False, shuffle=True, tau=None, gae=True, env=None,
                  replay_buffer=None, collector=None, logger=None, grad_clip=None, discount=0.99, num_epochs=3000,
                  batch_size=128, device="cpu", save_interval=100, eval_interval=1, save_dir=None, skip_nonfinite_steps=False,
-                 save_train_state=False, resume=None, **kwargs):
-        if optimizer_class is not None and optimizer_class is not torch.optim.Adam:
-            raise NotImplementedError("vision4leg_amd: PPO runs Adam on the HIP engine; optimizer_class must be Adam")
+                 save_train_state=False, resume=None, optimizer_kwargs=None, **kwargs):
+        # torch.optim.Adam / AdamW, a functools.partial of either, or "Adam" / "AdamW" + optimizer_kwargs (JSON configs): resolved
+        # the way the reference would build it, `optimizer_class(params, lr=..., eps=1e-5)` (a2c.py:30-40); anything else raises
+        opt = hip_optim.resolve(optimizer_class, optimizer_kwargs, lr=plr)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("vision4leg_amd: PPO needs a GPU device (got %s); there is no CPU path" % self.device)
@@ -217,9 +229,9 @@ class PPO:
         self.vf = vf
         self.to(self.device)
         self.plr, self.vlr = plr, vlr
-        self.optimizer_class = torch.optim.Adam
-        self.pf_optimizer = _HipAdam(self.pf.parameters(), lr=plr)
-        self.vf_optimizer = _HipAdam(self.vf.parameters(), lr=vlr)
+        self.optimizer_class = opt.optimizer_class
+        self.pf_optimizer = _HipAdam(self.pf.parameters(), plr, opt.eps, opt.betas, opt.weight_decay, opt.decoupled)
+        self.vf_optimizer = _HipAdam(self.vf.parameters(), vlr, opt.eps, opt.betas, opt.weight_decay, opt.decoupled)
         self.entropy_coeff = entropy_coeff
         self.clip_para = clip_para
         self.opt_epochs = opt_epochs
@@ -253,8 +265,9 @@ class PPO:
         self.use_graph = os.environ.get("V4L_GRAPH", "1") != "0"
         with torch.cuda.device(self.device):
             self.trainer = HipTrainer(self.pf.hip, self.vf.hip, self.target_pf.hip, batch_size, clip_para,
-                                      entropy_coeff, max_grad_norm=0.5, clipped_value_loss=clipped_value_loss,
-                                      world_size=self.world_size)
+                                      entropy_coeff, max_grad_norm=0.5, betas=opt.betas, eps=opt.eps,
+                                      clipped_value_loss=clipped_value_loss, world_size=self.world_size,
+                                      weight_decay=float(opt.weight_decay), decoupled=opt.decoupled)
             # The exchange. Preferred: the library's own RCCL communicator, whose two all-reduces are issued by update_next()
             # INSIDE the captured update graph (no host round trip between backward, all-reduce and Adam). It becomes the
             # schedule only after every rank has passed a self-test of that communicator through the very calls an update
@@ -470,6 +483,9 @@ class PPO:
         for name, network in self.snapshot_networks:
             files[name] = torch.load(osp.join(prefix, "model_{}_{}.pth".format(name, epoch)), map_location="cpu", weights_only=True)
             self._check_model_file(name, network, files[name], state)
+        for opt, key in ((self.pf_optimizer, "pf_optimizer"), (self.vf_optimizer, "vf_optimizer")):
+            for group in state[key]["param_groups"]:  # a file written under another optimiser setting: before anything is overwritten
+                opt.check_group(group)
         with torch.cuda.device(self.device):
             for name, network in self.snapshot_networks:
                 network.load_state_dict(files[name])

@@ -4,7 +4,7 @@ The HIP engine keeps each optimiser's Adam moments in two flat fp32 device buffe
 param_shapes / grad_offsets`, the layout `HipNet.grad_view` reads) and ONE step count per optimiser. `torch.optim.Adam` keeps
 `{"step", "exp_avg", "exp_avg_sq"}` per parameter, keyed by the position in `module.parameters()`. The functions here translate
 between the two, both ways, so that a run can be continued on either side (`torch.optim.Adam(net.parameters(), lr, eps=1e-5)`,
-torchrl/algo/a2c.py:24-27), and pack / unpack the parts of `train_state_{epoch}.pth` that are not tensors already.
+torchrl/algo/a2c.py:24-27; with weight decay `Adam(weight_decay=...)` or `AdamW`), and pack / unpack the parts of `train_state_{epoch}.pth` that are not tensors already.
 
 Nothing here touches the GPU or libv4l_hip.so: torch and numpy only (tests/test_resume_cpu.py).
 """
@@ -44,17 +44,22 @@ def flat_size(slices):
     return max((off + n for _, _, off, n in slices), default=0)
 
 
-def export_adam(slices, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-5):
+def export_adam(slices, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-5, weight_decay=0, decoupled=False):
     """Flat moment buffers + one step count -> what `torch.optim.Adam(...).state_dict()` returns after `step` steps: CPU fp32
-    copies in the parameters' shapes, `step` a float32 scalar tensor per parameter; an empty `state` before the first step."""
+    copies in the parameters' shapes, `step` a float32 scalar tensor per parameter; an empty `state` before the first step.
+    weight_decay goes into the group as given; `decoupled_weight_decay: True` is written only for a decoupled (AdamW) optimiser —
+    a real AdamW that loads a group without the key falls back to L2 decay (Adam.__setstate__), and an L2 / no-decay group stays
+    the six keys it always was."""
     state = {}
     if step > 0:
         m, v = exp_avg.detach().to("cpu", torch.float32), exp_avg_sq.detach().to("cpu", torch.float32)
         for i, (_, shp, off, n) in enumerate(slices):
             state[i] = {"step": torch.tensor(float(step), dtype=torch.float32),
                         "exp_avg": m[off:off + n].reshape(shp).clone(), "exp_avg_sq": v[off:off + n].reshape(shp).clone()}
-    group = {"lr": float(lr), "betas": (float(betas[0]), float(betas[1])), "eps": float(eps), "weight_decay": 0, "amsgrad": False,
+    group = {"lr": float(lr), "betas": (float(betas[0]), float(betas[1])), "eps": float(eps), "weight_decay": weight_decay, "amsgrad": False,
              "params": list(range(len(slices)))}
+    if decoupled:
+        group["decoupled_weight_decay"] = True
     return {"state": state, "param_groups": [group]}
 
 
@@ -77,8 +82,9 @@ def import_adam(slices, sd, total=None):
     ids = list(group["params"])
     if len(ids) != len(slices):
         raise ValueError("vision4leg_amd: the optimiser state covers %d parameters, the module has %d" % (len(ids), len(slices)))
-    if group.get("amsgrad") or group.get("weight_decay") or group.get("maximize"):
-        raise ValueError("vision4leg_amd: the HIP engine runs plain Adam (no amsgrad, weight_decay or maximize)")
+    for key in ("amsgrad", "maximize"):  # (weight decay is the caller's to compare with what it runs: the group is returned)
+        if group.get(key):
+            raise ValueError("vision4leg_amd: the HIP engine runs Adam / AdamW without %s" % key)
     total = flat_size(slices) if total is None else int(total)
     m, v = torch.zeros(total, dtype=torch.float32), torch.zeros(total, dtype=torch.float32)
     state, step = sd["state"], None
