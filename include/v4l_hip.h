@@ -146,7 +146,7 @@ const char* v4l_last_error(void);
 int v4l_version(void);
 /* sizeof(v4l_net_cfg / v4l_ppo_hyper / v4l_rollout) as THIS library was compiled: a binding whose struct mirrors differ (a
    stale libv4l_hip.so next to newer host code, or the other way round) must refuse to run instead of reading fields at the
-   wrong offsets. which: 0 net_cfg, 1 ppo_hyper, 2 rollout; anything else: -1 */
+   wrong offsets. which: 0 net_cfg, 1 ppo_hyper, 2 rollout, 4 vmpo_hyper; anything else (3 included): -1 */
 int v4l_abi_sizeof(int which);
 
 /* ---- network plan: replaces the nn.Module constructors' shape bookkeeping (nets.py / base.py above) ---- */
@@ -387,6 +387,45 @@ int v4l_trainer_update(v4l_trainer* tr, const v4l_rollout* ro, const int* rowidx
                        double lr_pf, double lr_vf, int64_t step, float* stats_dev, void* stream);
 /* copy_model_params_from_to(pf, target_pf) (torchrl/algo/utils.py:23-25, ppo.py:34) + repack of the target */
 int v4l_trainer_sync_target(v4l_trainer* tr, void* stream);
+
+/* ---- V-MPO minibatch update (version 110): replaces VMPO.update_actor (torchrl/algo/on_policy/v_mpo.py:58-134) — the critic
+ * step, the advantage statistics and both clip + Adam launches are the PPO phases above with clipped_value_loss = 0
+ * (v_mpo.py:136-155, 173-182). One update = v4l_trainer_begin, then eagerly v4l_trainer_critic_grads, v4l_trainer_critic_step,
+ * v4l_trainer_vmpo_actor_grads, v4l_trainer_actor_step (no hipGraph of a V-MPO update yet). Single process only. ---- */
+typedef struct v4l_vmpo_hyper {
+  double eta_eps;   /* v_mpo.py:20,27: 0.02 */
+  double alpha_eps; /* v_mpo.py:21,31: 0.1  */
+  double eta0;      /* v_mpo.py:28: 1   */
+  double alpha0;    /* v_mpo.py:32: 0.1 */
+  double lr_scale;  /* 1: the two scalars' optimiser runs at the policy's learning rate (v_mpo.py:35-39). 0: eta, alpha and their
+                       optimiser state are left untouched (tests that look at one loss evaluation's gradients) */
+} v4l_vmpo_hyper;
+#define V4L_VMPO_STATS 12 /* floats per update in the V-MPO record: [0] Training/alpha_loss, [1] Training/alpha, [2] Training/eta
+                             (both after the step and the clamp), [3..6] KL/mean, std, max, min (v_mpo.py:119-132), [7] d(loss)/d(eta),
+                             [8] d(loss)/d(alpha) (diagnostic), rest 0 */
+#define V4L_VMPO_STATE 7  /* doubles of v4l_trainer_vmpo_state: eta, alpha, Adam exp_avg of eta, of alpha, exp_avg_sq of eta, of
+                             alpha, step count */
+/* bytes of the device block that holds eta, alpha, their optimiser state, the record being filled and the selected rows of a
+ * minibatch of up to n_max rows */
+int64_t v4l_trainer_vmpo_bytes(const v4l_trainer* tr, int n_max);
+/* VMPO.__init__ (v_mpo.py:27-39): registers the caller-allocated block (v4l_trainer_vmpo_bytes(n_max) bytes, 256-byte aligned, valid
+ * until the next init / destroy) and writes eta0, alpha0 and a fresh optimiser state into it on `stream`. */
+int v4l_trainer_vmpo_init(v4l_trainer* tr, const v4l_vmpo_hyper* vhp, void* block_dev, int n_max, void* stream);
+/* VMPO.update_actor (v_mpo.py:58-134) up to and including loss.backward() and param_optimizer.step(): the descending sort +
+ * chunk(2) as v4l_vmpo_select over the update's rows (m = ceil(n / 2) kept), the frozen target policy and the live policy on
+ * those m rows (the target on the auxiliary stream), the V-MPO loss launch — loss gradients w.r.t. mean / log sigma, the
+ * statistics, and the Adam (AdamW, weight decay: hp's) step + clamp at 1e-8 of eta and alpha with the run's lr_pf — and the
+ * backward into the policy's gradient buffer. v4l_trainer_actor_step follows. vstats_all_dev: [U][V4L_VMPO_STATS] records of the
+ * run opened by v4l_trainer_begin (row = the update's index) or NULL. ro->logp_old_dev is ignored: the KL needs the target's
+ * mean and sigma (v_mpo.py:81-96). hp->world_size must be 1. */
+int v4l_trainer_vmpo_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* vstats_all_dev,
+                                 void* stream);
+/* eta, alpha and the state of their optimiser (V4L_VMPO_STATE doubles), read back (synchronises the stream) / written */
+int v4l_trainer_vmpo_state(v4l_trainer* tr, double* out, void* stream);
+int v4l_trainer_vmpo_set_state(v4l_trainer* tr, const double* in, void* stream);
+/* The selection alone (v_mpo.py:65-67): sel_dev[r] = the slot (rowidx_dev[i], or i when rowidx_dev is NULL) of the row with the
+ * r-th largest adv_dev[slot], r < ceil(n / 2); ties to the earlier i, NaN after every number. n >= 1. */
+int v4l_vmpo_select(const float* adv_dev, const int* rowidx_dev, int n, int* sel_dev, void* stream);
 
 /* ---- data parallel: one process per GPU, every rank owns an env shard and its own rollout; gradients are
  * summed with ONE in-place RCCL all-reduce per optimiser step on the flat gradient buffer. The reference has no

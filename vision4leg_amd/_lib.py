@@ -19,6 +19,8 @@ ST_NONFINITE = 22   # record slot: number of NaN / Inf among the 18 logged scala
 ST_F16_SAT = 23     # record slot: V4L_F16 — loss-gradient elements of the update clamped at +-V4L_F16_GRAD_CLAMP
 V4L_OUT_LD = 16
 V4L_MAX_ACT = 16   # widest action vector of a policy (include/v4l_hip.h)
+V4L_VMPO_STATS = 12   # floats per update in the V-MPO record (include/v4l_hip.h)
+V4L_VMPO_STATE = 7    # doubles of v4l_trainer_vmpo_state: eta, alpha, exp_avg x 2, exp_avg_sq x 2, step
 V4L_BUCKET_TAIL = 8   # scalars behind the gradients of an all-reduce bucket
 V4L_COMM_ID_BYTES = 128
 
@@ -49,6 +51,17 @@ class PPOHyper(C.Structure):
     ("clipped_value_loss", C.c_int), ("world_size", C.c_int),
     ("weight_decay", C.c_double), ("decoupled_weight_decay", C.c_int),
   ]
+
+
+# the V-MPO record's logger keys, in record order (torchrl/algo/on_policy/v_mpo.py:119-132); slots 7, 8: d(loss)/d(eta), d(alpha)
+VMPO_STAT_KEYS = ["Training/alpha_loss", "Training/alpha", "Training/eta", "KL/mean", "KL/std", "KL/max", "KL/min"]
+# the 19 keys VMPO.update returns, in the reference's order: 12 of the PPO record (no log_std/*, no ratio/*) + the 7 above
+VMPO_INFO_KEYS = (STAT_KEYS[:7] + VMPO_STAT_KEYS[:3] + STAT_KEYS[7:11] + VMPO_STAT_KEYS[3:] + ["grad_norm/pf"])
+
+
+class VMPOHyper(C.Structure):
+  _fields_ = [("eta_eps", C.c_double), ("alpha_eps", C.c_double), ("eta0", C.c_double), ("alpha0", C.c_double),
+              ("lr_scale", C.c_double)]
 
 
 class Rollout(C.Structure):
@@ -139,6 +152,12 @@ _SIGS = {
   "v4l_trainer_update": (C.c_int, [_P, C.POINTER(Rollout), _P, C.c_int, C.POINTER(PPOHyper), C.c_double,
                                    C.c_double, C.c_int64, _P, _P]),
   "v4l_trainer_sync_target": (C.c_int, [_P, _P]),
+  "v4l_trainer_vmpo_bytes": (C.c_int64, [_P, C.c_int]),
+  "v4l_trainer_vmpo_init": (C.c_int, [_P, C.POINTER(VMPOHyper), _P, C.c_int, _P]),
+  "v4l_trainer_vmpo_actor_grads": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), _P, _P]),
+  "v4l_trainer_vmpo_state": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
+  "v4l_trainer_vmpo_set_state": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
+  "v4l_vmpo_select": (C.c_int, [_P, _P, C.c_int, _P, _P]),
   "v4l_comm_available": (C.c_int, []),
   "v4l_trainer_comm_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
   "v4l_comm_unique_id": (C.c_int, [C.c_char_p]),
@@ -193,7 +212,8 @@ def lib():
       raise RuntimeError("vision4leg_amd: %s predates this Python binding (%s) — %s" % (LIB_PATH, e, rebuild)) from None
     # the struct mirrors above must be the structs this library was compiled with (a stale .so next to newer host code reads
     # fields at the wrong offsets otherwise)
-    for which, (name, mirror) in enumerate((("v4l_net_cfg", NetCfg), ("v4l_ppo_hyper", PPOHyper), ("v4l_rollout", Rollout))):
+    for which, (name, mirror) in ((0, ("v4l_net_cfg", NetCfg)), (1, ("v4l_ppo_hyper", PPOHyper)), (2, ("v4l_rollout", Rollout)),
+                                  (4, ("v4l_vmpo_hyper", VMPOHyper))):
       have = l.v4l_abi_sizeof(which)
       if have != C.sizeof(mirror):
         raise RuntimeError("vision4leg_amd: %s was compiled with sizeof(%s) = %d, the Python binding expects %d — %s"

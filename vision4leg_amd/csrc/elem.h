@@ -1004,6 +1004,225 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const ParamSeg* __restri
   v[o] = vv;
 }
 
+#pragma clang fp contract(on)  // (per-statement contraction, as for the PPO loss rows above)
+// --------------------------------------------------------------------------------- V-MPO (torchrl/algo/on_policy/v_mpo.py)
+// VMPO.update_actor's `torch.sort(advs, descending=True)` + `idx.chunk(2)` (v_mpo.py:65-67) by counting: sel[r] = the rollout
+// slot of the minibatch row with the r-th largest advantage, r < m = ceil(n / 2). One thread per row, the n advantages staged
+// through LDS 256 at a time (every lane reads the same LDS words: a broadcast), rank_i = #{j : adv_j > adv_i or (adv_j == adv_i
+// and j < i)}: a strict total order, so the ranks are a permutation of 0 .. n-1 and every sel entry has exactly one writer — no
+// atomics, the same output every run. Ties go to the earlier minibatch position (torch leaves their order unspecified); a NaN
+// compares as smaller than every number (NaNs among themselves by position), so sel is written whole and in bounds whatever
+// the advantages hold. rowidx null: row i is slot i.
+// The order as one integer compare: the float mapped monotonically to an unsigned (NaN -> 0, below -inf's image; -0 == +0) in the
+// high word, 0x7fffffff - position in the low one — key_j > key_i <=> row j sorts before row i. 0 is no row's key (padding).
+__device__ __forceinline__ unsigned long long vmpo_key(float a, int j) {
+  const unsigned u = a == 0.f ? 0u : __float_as_uint(a);
+  const unsigned k = a != a ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
+  return ((unsigned long long)k << 32) | (unsigned)(0x7fffffff - j);
+}
+__global__ __launch_bounds__(256) void vmpo_select_kernel(const float* __restrict__ adv, const int* __restrict__ rowidx, int n,
+                                                          int* __restrict__ sel) {
+  __shared__ __align__(16) unsigned long long tile[256];
+  const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  const bool mine = i < n;
+  const int slot = mine ? (rowidx ? rowidx[i] : i) : 0;
+  const unsigned long long ki = vmpo_key(mine ? adv[slot] : 0.f, i);
+  int rank = 0;
+  for (int t0 = 0; t0 < n; t0 += 256) {
+    const int j = t0 + (int)threadIdx.x;
+    const unsigned long long kj = j < n ? vmpo_key(adv[rowidx ? rowidx[j] : j], j) : 0ull;
+    __syncthreads();  // the previous tile has been read by every thread
+    tile[threadIdx.x] = kj;
+    __syncthreads();
+    const ulonglong2* t2 = reinterpret_cast<const ulonglong2*>(tile);  // 16-byte LDS reads, several in flight
+#pragma unroll 8
+    for (int k = 0; k < 128; ++k) {
+      const ulonglong2 v = t2[k];
+      rank += (v.x > ki ? 1 : 0) + (v.y > ki ? 1 : 0);
+    }
+  }
+  const int m = (n + 1) / 2;
+  if (mine && rank < m) sel[rank] = slot;
+}
+
+// The two learnable scalars of V-MPO (eta: temperature of the advantage softmax, alpha: weight of the KL term; v_mpo.py:27-39)
+// with the state of their optimiser, `optimizer_class([eta, alpha], lr=plr, eps=1e-5)`: one device block the trainer owns.
+struct VmpoState { double eta, alpha, m[2], v[2]; long long step; };  // m / v: Adam moments of [0] eta, [1] alpha
+// V4L_VMPO_STATS floats per update, next to the PPO record: the seven logger scalars V-MPO adds (v_mpo.py:119-132) and the two
+// scalar gradients (diagnostic)
+enum { VST_ALPHA_LOSS = 0, VST_ALPHA, VST_ETA, VST_KL_MEAN, VST_KL_STD, VST_KL_MAX, VST_KL_MIN, VST_DETA, VST_DALPHA, VST_SIZE = 12 };
+struct VmpoArgs {
+  VmpoState* vs;
+  float *vst_cur, *vst_all;  // the record being filled; [U][VST_SIZE] records of the run (row ctl->upd_index) or null
+  const UpdCtl* ctl;         // lr_pf, betas, weight decay of the open run
+  double eta_eps, alpha_eps;
+  double lr_scale;           // 1; 0 leaves eta, alpha and their optimiser state untouched (tests look at the gradients alone)
+  float adam_eps;
+};
+// VMPO.update_actor's loss (v_mpo.py:75-102) on the m selected rows (p.rowidx = sel, p.n = m, p.inv_n = 1 / m) and its gradient
+// w.r.t. the policy mean [m][OUT_LD], log sigma [A], eta and alpha; single block, the sibling of actor_loss_kernel.
+//   phis = softmax(an / eta)                       an: the advantage normalised with the WHOLE minibatch's statistics (p.st)
+//   policy_loss = mean_i(-phis_i logp_i + alpha kl_i)       kl_i = sum_a KL(N(mu, sigma) || N(mu_t, sigma_t)): plain Normals also
+//                                                           for tanh_action policies (continuous_policy.py:127-146)
+//   eta_loss = eta eta_eps + eta log(mean(exp(an / eta)))   alpha_loss = alpha alpha_eps - alpha mean(kl)
+// Pass 1: max and sum of exp(an / eta - max) (the reference does not subtract the max; the same value while it does not
+// overflow). Pass 2: the rows. Thread 0 then takes the Adam / AdamW step of the two scalars in double, clamps them at 1e-8
+// (v_mpo.py:113-117) and files the V-MPO record. Fills the PPO record's shared slots as actor_loss_body does (ratio =
+// exp(logp - logp_target)), so the closing Adam launch's non-finite count works unchanged.
+template <bool TANH, int CAP>
+__global__ __launch_bounds__(1024) void vmpo_loss_kernel(ActorArgs p, VmpoArgs q) {
+  __shared__ float sdl[16][CAP];
+  const int m = p.n, A = p.A;
+  const ActorDimsT<CAP> D = actor_dims<CAP>(p);
+  float dl[CAP];
+#pragma unroll
+  for (int a = 0; a < CAP; ++a) dl[a] = 0.f;
+  const float amean = p.st[ST_ADV_MEAN], astd = p.st[ST_ADV_STD];
+  const double eta_d = q.vs->eta, alpha_d = q.vs->alpha;
+  const float eta = (float)eta_d, alpha = (float)alpha_d;
+  // the thread's first row (its only one while m <= blockDim.x): slot and normalised advantage stay in registers over the passes
+  const int i0 = (int)threadIdx.x;
+  const int slot0 = i0 < m ? p.rowidx[i0] : 0;
+  const float an0 = i0 < m ? (p.adv[slot0] - amean) / (astd + 1e-5f) : 0.f;
+  // ---- pass 1
+  float xmx = -INFINITY;
+  for (int i = threadIdx.x; i < m; i += blockDim.x) {
+    const float an = i == i0 ? an0 : (p.adv[p.rowidx[i]] - amean) / (astd + 1e-5f);
+    xmx = fmaxf(xmx, an / eta);
+  }
+  const float xmax = block_red4(0.0, 0.0, xmx, 0.f).mx;
+  double se = 0.0, sea = 0.0;
+  for (int i = threadIdx.x; i < m; i += blockDim.x) {
+    const float an = i == i0 ? an0 : (p.adv[p.rowidx[i]] - amean) / (astd + 1e-5f);
+    const float e = expf(an / eta - xmax);
+    se += e; sea += (double)e * an;
+  }
+  const Red4 r0 = block_red4(se, sea, 0.f, 0.f);
+  const float esum = (float)r0.s;
+  // ---- pass 2
+  double s_lp = 0.0, s_lp2 = 0.0, s_kl = 0.0, s_kl2 = 0.0, s_loss = 0.0;
+  int sat = 0;
+  float lp_mx = -INFINITY, lp_mn = INFINITY, kl_mx = -INFINITY, kl_mn = INFINITY, r_mx = -INFINITY, r_mn = INFINITY;
+  for (int i = threadIdx.x; i < m; i += blockDim.x) {
+    const int slot = i == i0 ? slot0 : p.rowidx[i];
+    const float an = i == i0 ? an0 : (p.adv[slot] - amean) / (astd + 1e-5f);
+    const float phi = expf(an / eta - xmax) / esum;
+    float mu[CAP], tmu[CAP], dmr[CAP];
+    actor_load_row(p.mean + (int64_t)i * OUT_LD, mu);
+    actor_load_row(p.tmean + (int64_t)i * OUT_LD, tmu);
+    float lp = 0.f, lpt = 0.f, kl = 0.f;
+#pragma unroll
+    for (int a = 0; a < CAP; ++a) {
+      dmr[a] = 0.f;
+      if (a < A) {
+        const float act = p.acts[(int64_t)slot * A + a];
+        const float x = TANH ? tanh_pre(act) : act;
+        const float corr = TANH ? tanh_corr(act) : 0.f;
+        const float d = x - mu[a], dt = x - tmu[a], dmu = mu[a] - tmu[a];
+        const float var = D.sg[a] * D.sg[a], tvar = D.tsg[a] * D.tsg[a];
+        lp += -(d * d) / (2.f * var) - D.lsg[a] - HALF_LOG_2PI - corr;
+        lpt += -(dt * dt) / (2.f * tvar) - D.tlsg[a] - HALF_LOG_2PI - corr;
+        // torch.distributions.kl._kl_normal_normal: 0.5 (var_ratio + t1 - 1 - log(var_ratio))
+        const float sr = D.sg[a] / D.tsg[a], vr = sr * sr, t1 = (dmu / D.tsg[a]) * (dmu / D.tsg[a]);
+        kl += 0.5f * (vr + t1 - 1.f - logf(vr));
+        dmr[a] = grad_out(p.inv_n * (-phi * (d / var) + alpha * (dmu / tvar)), p.gscale, sat);
+        dl[a] += p.inv_n * (-phi * (d * d / var - 1.f) + alpha * (vr - 1.f));
+      }
+    }
+    actor_store_dmean(p.dmean + (int64_t)i * OUT_LD, dmr, true);
+    const float ratio = expf(lp - lpt);
+    s_loss += (double)(-phi * lp + alpha * kl);
+    s_lp += lp; s_lp2 += (double)lp * lp;
+    s_kl += kl; s_kl2 += (double)kl * kl;
+    lp_mx = fmaxf(lp_mx, lp); lp_mn = fminf(lp_mn, lp);
+    kl_mx = fmaxf(kl_mx, kl); kl_mn = fminf(kl_mn, kl);
+    r_mx = fmaxf(r_mx, ratio); r_mn = fminf(r_mn, ratio);
+  }
+  const Red4 r1 = block_red4(s_lp, s_lp2, lp_mx, lp_mn);
+  const Red4 r2 = block_red4(s_kl, s_kl2, kl_mx, kl_mn);
+  const Red4 r3 = block_red4(s_loss, (double)sat, r_mx, r_mn);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int a = 0; a < CAP; ++a) {
+    const float v = wave_sum(dl[a]);
+    if (lane == 0) sdl[w][a] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < A) {
+    const int a = threadIdx.x;
+    const float raw = p.logstd[a];
+    float g = 0.f;
+    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) g += sdl[k][a];
+    p.dlogstd[a] = (raw >= LOG_SIG_MIN && raw <= LOG_SIG_MAX) ? g : 0.f;  // the clamp of continuous_policy.py:486-492 passes no gradient outside
+  }
+  if (threadIdx.x == 0) {
+    float* st = p.st;
+    const double dm = (double)m;
+    const double lpm = r1.s / dm, klm = r2.s / dm;
+    st[ST_PI_LOSS] = (float)(r3.s / dm);
+    st[ST_LP_MEAN] = (float)lpm;
+    st[ST_LP_STD] = (float)sqrt(fmax(0.0, (r1.s2 - dm * lpm * lpm) / (dm - 1.0)));
+    st[ST_LP_MAX] = r1.mx; st[ST_LP_MIN] = r1.mn;
+    st[ST_RATIO_MAX] = r3.mx; st[ST_RATIO_MIN] = r3.mn;
+    if (p.gscale != 1.f) st[ST_F16_SAT] += (float)r3.s2;
+    double lm = 0.0; float lmx = -INFINITY, lmn = INFINITY;
+#pragma unroll
+    for (int a = 0; a < CAP; ++a)
+      if (a < A) { lm += D.ls[a]; lmx = fmaxf(lmx, D.ls[a]); lmn = fminf(lmn, D.ls[a]); }
+    lm /= A;
+    double lq = 0.0;
+#pragma unroll
+    for (int a = 0; a < CAP; ++a)
+      if (a < A) lq += (D.ls[a] - lm) * (D.ls[a] - lm);
+    st[ST_LS_MEAN] = (float)lm;
+    st[ST_LS_STD] = A > 1 ? (float)sqrt(lq / (A - 1)) : NAN;
+    st[ST_LS_MAX] = lmx; st[ST_LS_MIN] = lmn;
+    // d(eta_loss)/d(eta) = eta_eps + log(mean(exp(an / eta))) - (sum_i phis_i an_i) / eta;  d(alpha_loss)/d(alpha) = alpha_eps - mean(kl)
+    const double lme = (double)xmax + log(r0.s / dm);
+    const double grad[2] = {q.eta_eps + lme - (r0.s2 / r0.s) / eta_d, q.alpha_eps - klm};
+    VmpoState s = *q.vs;
+    double par[2] = {s.eta, s.alpha};
+    if (q.lr_scale != 0.0) {
+      // torch/optim/adam.py::_single_tensor_adam on two one-element tensors, in double; the parameters are kept as the fp32
+      // values the reference's tensors would hold
+      const double lr = q.ctl->lr_pf * q.lr_scale, b1 = (double)q.ctl->beta1, b2 = (double)q.ctl->beta2;
+      const double wd = q.ctl->weight_decay;
+      s.step += 1;
+      const double bc1 = 1.0 - pow(b1, (double)s.step), bc2 = 1.0 - pow(b2, (double)s.step);
+      for (int k = 0; k < 2; ++k) {
+        double g = grad[k], pp = par[k];
+        if (wd > 0.0 && q.ctl->decoupled) pp *= 1.0 - lr * wd;
+        if (wd > 0.0 && !q.ctl->decoupled) g += wd * pp;
+        s.m[k] += (g - s.m[k]) * (1.0 - b1);
+        s.v[k] = s.v[k] * b2 + (1.0 - b2) * g * g;
+        pp -= (lr / bc1) * (s.m[k] / (sqrt(s.v[k]) / sqrt(bc2) + (double)q.adam_eps));
+        par[k] = (double)(float)fmax(pp, 1e-8);  // torch.clamp(min=1e-8), v_mpo.py:115-117 (a NaN stays a NaN)
+      }
+      s.eta = par[0]; s.alpha = par[1];
+      *q.vs = s;
+    }
+    float rec[VST_SIZE];
+#pragma unroll
+    for (int k = 0; k < VST_SIZE; ++k) rec[k] = 0.f;
+    rec[VST_ALPHA_LOSS] = (float)(alpha_d * q.alpha_eps - alpha_d * klm);  // with the alpha the loss was formed with
+    rec[VST_ALPHA] = (float)par[1]; rec[VST_ETA] = (float)par[0];       // after the step and the clamp (v_mpo.py:121-122)
+    rec[VST_KL_MEAN] = (float)klm;
+    rec[VST_KL_STD] = (float)sqrt(fmax(0.0, (r2.s2 - dm * klm * klm) / (dm - 1.0)));
+    rec[VST_KL_MAX] = r2.mx; rec[VST_KL_MIN] = r2.mn;
+    rec[VST_DETA] = (float)grad[0]; rec[VST_DALPHA] = (float)grad[1];
+    const int64_t u = q.ctl->upd_index;
+#pragma unroll
+    for (int k = 0; k < VST_SIZE; ++k) {
+      q.vst_cur[k] = rec[k];
+      if (q.vst_all != nullptr) q.vst_all[u * VST_SIZE + k] = rec[k];
+    }
+  }
+}
+__global__ void vmpo_state_set_kernel(VmpoState* vs, double eta, double alpha, double m0, double m1, double v0, double v1, long long step) {
+  vs->eta = eta; vs->alpha = alpha; vs->m[0] = m0; vs->m[1] = m1; vs->v[0] = v0; vs->v[1] = v1; vs->step = step;
+}
+#pragma clang fp contract(fast)
+
 // --------------------------------------------------------------------------------- weight packing
 // Builds the contraction-ready copies of a weight tensor (operand type T, zero padded to the GEMM tiles).
 enum { PK_NT = 0, PK_T = 1, PK_CONV_NHWC = 2, PK_CONV_NHWC_T = 3, PK_CONV_DGRAD = 4, PK_FRAG = 5, PK_FRAGP = 6, PK_FRAGPT = 7, PK_FRAGT = 8 };

@@ -246,4 +246,10 @@ struct v4l_trainer {
   // data parallel: RCCL communicator of this trainer's process group (null: single GPU, or the host drives the exchange)
   void* comm = nullptr;
   int comm_rank = 0, comm_world = 1;
+  // V-MPO (v4l_trainer_vmpo_init): the caller's device block [VmpoState | record being filled | selected rows] and the hyper-parameters
+  v4l::VmpoState* vmpo = nullptr;
+  float* vmpo_stats_cur = nullptr;
+  int* vmpo_sel = nullptr;
+  int vmpo_n_max = 0;
+  v4l_vmpo_hyper vmpo_hp = {};
 };

@@ -2630,13 +2630,29 @@ static int launch_actor_loss(hipStream_t s, const ActorArgs& aa, dim3 blk) {
   return 0;
 }
 
+// V-MPO: the row selection and the single-block loss launch (csrc/elem.h)
+static int launch_vmpo_select(hipStream_t s, const float* adv, const int* rowidx, int n, int* sel) {
+  g_op = "select";
+  V4L_KLAUNCH("vmpo_select", 0, s, vmpo_select_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, adv, rowidx, n, sel);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
+template <int CAP>
+static int launch_vmpo_loss(hipStream_t s, const ActorArgs& aa, const VmpoArgs& va, dim3 blk) {
+  if (aa.tanh_action) V4L_KLAUNCH("vmpo_loss", 0, s, (vmpo_loss_kernel<true, CAP>), dim3(1), blk, 0, s, aa, va);
+  else V4L_KLAUNCH("vmpo_loss", 0, s, (vmpo_loss_kernel<false, CAP>), dim3(1), blk, 0, s, aa, va);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 extern "C" {
 
 const char* v4l_last_error(void) { return v4l::last_error(); }
-int v4l_version(void) { return 109; }  // v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
+int v4l_version(void) { return 110; }  // V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
 int v4l_abi_sizeof(int which) {
-  return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) : -1;
+  return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) :
+         which == 4 ? (int)sizeof(v4l_vmpo_hyper) : -1;  // (3 stays unassigned)
 }
 
 int v4l_net_create(const v4l_net_cfg* cfg, v4l_net** out) {
@@ -3612,6 +3628,108 @@ int v4l_trainer_actor_step(v4l_trainer* tr, const v4l_ppo_hyper* hp, void* strea
   // the policy's Adam launch also closes the update (statistics record out, minibatch index + 1)
   return adam_step(tr, tr->pf, tr->g_pf, tr->m_pf, tr->v_pf, hp, 0, st + ST_GN_PF, s, true);
 }
+
+// ---- V-MPO (torchrl/algo/on_policy/v_mpo.py): the actor stage of an update whose other phases are PPO's
+int v4l_vmpo_select(const float* adv_dev, const int* rowidx_dev, int n, int* sel_dev, void* stream) {
+  V4L_REQUIRE(adv_dev && sel_dev && n >= 1, "v4l_vmpo_select: bad argument");
+  return launch_vmpo_select((hipStream_t)stream, adv_dev, rowidx_dev, n, sel_dev);
+}
+int64_t v4l_trainer_vmpo_bytes(const v4l_trainer* tr, int n_max) {
+  if (!tr || n_max <= 0) return -1;
+  static_assert(sizeof(VmpoState) <= 128 && VST_SIZE * sizeof(float) <= 128, "V-MPO block layout [VmpoState | record | rows]");
+  return 256 + (int64_t)round_up((n_max + 1) / 2, 64) * sizeof(int);
+}
+static int vmpo_write_state(v4l_trainer* tr, const double* v, hipStream_t s) {
+  hipLaunchKernelGGL(vmpo_state_set_kernel, dim3(1), dim3(1), 0, s, tr->vmpo, v[0], v[1], v[2], v[3], v[4], v[5], (long long)v[6]);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
+int v4l_trainer_vmpo_init(v4l_trainer* tr, const v4l_vmpo_hyper* vhp, void* block_dev, int n_max, void* stream) {
+  V4L_REQUIRE(tr && vhp && block_dev && n_max > 1, "v4l_trainer_vmpo_init: bad argument");
+  V4L_REQUIRE(((uintptr_t)block_dev & 255) == 0, "v4l_trainer_vmpo_init: the block must be 256-byte aligned");
+  V4L_REQUIRE(vhp->eta0 > 0.0 && vhp->alpha0 > 0.0 && vhp->eta0 <= 3.0e38 && vhp->alpha0 <= 3.0e38,
+              "v4l_vmpo_hyper: eta0 and alpha0 must be finite and > 0 (got %g, %g)", vhp->eta0, vhp->alpha0);
+  V4L_REQUIRE(vhp->eta_eps == vhp->eta_eps && vhp->alpha_eps == vhp->alpha_eps && (vhp->lr_scale == 0.0 || vhp->lr_scale == 1.0),
+              "v4l_vmpo_hyper: eta_eps / alpha_eps must be numbers and lr_scale 0 or 1");
+  tr->vmpo = (VmpoState*)block_dev;
+  tr->vmpo_stats_cur = (float*)((char*)block_dev + 128);
+  tr->vmpo_sel = (int*)((char*)block_dev + 256);
+  tr->vmpo_n_max = n_max;
+  tr->vmpo_hp = *vhp;
+  const double fresh[V4L_VMPO_STATE] = {(double)(float)vhp->eta0, (double)(float)vhp->alpha0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  return vmpo_write_state(tr, fresh, (hipStream_t)stream);
+}
+int v4l_trainer_vmpo_state(v4l_trainer* tr, double* out, void* stream) {
+  V4L_REQUIRE(tr && tr->vmpo && out, "v4l_trainer_vmpo_state: no V-MPO state (v4l_trainer_vmpo_init)");
+  hipStream_t s = (hipStream_t)stream;
+  VmpoState h;
+  V4L_HIP_CHECK(hipMemcpyAsync(&h, tr->vmpo, sizeof(h), hipMemcpyDeviceToHost, s));
+  V4L_HIP_CHECK(hipStreamSynchronize(s));
+  out[0] = h.eta; out[1] = h.alpha; out[2] = h.m[0]; out[3] = h.m[1]; out[4] = h.v[0]; out[5] = h.v[1]; out[6] = (double)h.step;
+  return 0;
+}
+int v4l_trainer_vmpo_set_state(v4l_trainer* tr, const double* in, void* stream) {
+  V4L_REQUIRE(tr && tr->vmpo && in, "v4l_trainer_vmpo_set_state: no V-MPO state (v4l_trainer_vmpo_init)");
+  V4L_REQUIRE(in[0] > 0.0 && in[1] > 0.0 && in[4] >= 0.0 && in[5] >= 0.0 && in[6] >= 0.0,
+              "v4l_trainer_vmpo_set_state: eta, alpha must be > 0, the second moments and the step count >= 0");
+  return vmpo_write_state(tr, in, (hipStream_t)stream);
+}
+int v4l_trainer_vmpo_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* vstats_all_dev,
+                                 void* stream) {
+  int rc = check_update_args(tr, ro, n, hp);
+  if (rc) return rc;
+  V4L_REQUIRE(tr->vmpo != nullptr, "v4l_trainer_vmpo_actor_grads: no V-MPO state (v4l_trainer_vmpo_init)");
+  V4L_REQUIRE(n <= tr->vmpo_n_max, "v4l_trainer_vmpo_actor_grads: n = %d is over the V-MPO block's n_max = %d", n, tr->vmpo_n_max);
+  V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_vmpo_actor_grads: V-MPO runs in a single process");
+  hipStream_t s = (hipStream_t)stream;
+  V4L_REQUIRE(!capturing(s), "v4l_trainer_vmpo_actor_grads: a V-MPO update is a sequence of eager launches (no stream capture)");
+  v4l_net *pf = tr->pf, *tp = tr->tpf;
+  const int m = (n + 1) / 2;  // idx.chunk(2)[0], v_mpo.py:67
+  const int* sel = tr->vmpo_sel;
+  // 1. the better half of the minibatch, on the device (nothing below waits for the host)
+  if ((rc = launch_vmpo_select(s, ro->advs_dev, tr->rowidx_cur, n, tr->vmpo_sel))) return rc;
+  const Layout Lp = pf->layout(m), Lt = tp->layout(m);
+  float* ws_t = tr->ws + std::max(pf->layout(n).total, tr->vf->layout(n).total);
+  // 2. the frozen target policy on those rows, next to the live policy's repack + forward (v4l_trainer_actor_grads' fork)
+  hipStream_t s_tgt = s;
+  const bool par_tgt = tr->aux != nullptr;
+  if (par_tgt) {
+    V4L_HIP_CHECK(hipEventRecord(tr->ev_fork, s));
+    V4L_HIP_CHECK(hipStreamWaitEvent(tr->aux, tr->ev_fork, 0));
+    s_tgt = tr->aux;
+  }
+  { PhaseScope ps("tpf.fwd");
+  if ((rc = v4l_net_forward(tp, ro->state_dev, ro->image_dev, sel, m, ws_t, 0, (void*)s_tgt))) return rc; }
+  if ((rc = v4l_net_pack(pf, stream))) return rc;  // 3. the critic step moved the shared encoder
+  { PhaseScope ps("pf.fwd");  // 4. forward, loss and backward as launches of their own (the fused launch's loss is PPO's)
+  if ((rc = v4l_net_forward(pf, ro->state_dev, ro->image_dev, sel, m, tr->ws, 1, stream))) return rc; }
+  if (par_tgt) {
+    V4L_HIP_CHECK(hipEventRecord(tr->ev_join, tr->aux));
+    V4L_HIP_CHECK(hipStreamWaitEvent(s, tr->ev_join, 0));
+  }
+  g_op = "loss";
+  {
+    ActorArgs aa;
+    memset(&aa, 0, sizeof(aa));
+    aa.mean = tr->ws + Lp.out; aa.logstd = pf->p[pf->logstd];
+    aa.tmean = ws_t + Lt.out; aa.tlogstd = tp->p[tp->logstd];
+    aa.logp_old = nullptr; aa.acts = ro->acts_dev; aa.adv = ro->advs_dev; aa.rowidx = sel;
+    aa.n = m; aa.A = pf->cfg.out_dim; aa.inv_n = 1.f / (float)m; aa.clip = 0.f; aa.ent_coef = 0.f;  // entropy_coeff: accepted, unused (v_mpo.py)
+    aa.dmean = tr->ws + Lp.dout; aa.dlogstd = tr->g_pf + pf->params[pf->logstd].goff; aa.st = tr->stats_cur;
+    aa.tanh_action = pf->cfg.tanh_action;
+    aa.gscale = v4l_net_grad_scale(pf, m);
+    VmpoArgs va;
+    memset(&va, 0, sizeof(va));
+    va.vs = tr->vmpo; va.vst_cur = tr->vmpo_stats_cur; va.vst_all = vstats_all_dev; va.ctl = tr->ctl;
+    va.eta_eps = tr->vmpo_hp.eta_eps; va.alpha_eps = tr->vmpo_hp.alpha_eps; va.lr_scale = tr->vmpo_hp.lr_scale; va.adam_eps = hp->eps;
+    const dim3 blk(m >= 512 ? 1024 : 256);
+    rc = act_cap(aa.A) != ACT_CAP_NARROW ? launch_vmpo_loss<V4L_MAX_ACT>(s, aa, va, blk) : launch_vmpo_loss<ACT_CAP_NARROW>(s, aa, va, blk);  // 5.
+    if (rc) return rc;
+  }
+  PhaseScope ps("pf.bwd");  // 6.
+  return v4l_net_backward(pf, ro->state_dev, ro->image_dev, sel, m, tr->ws, tr->g_pf, stream);
+}
+
 
 int v4l_comm_available(void) { return rccl_load(); }
 int v4l_trainer_comm_info(const v4l_trainer* tr, int* rank_out, int* world_out) {

@@ -1,3 +1,3 @@
-from .on_policy import PPO  # noqa: F401
+from .on_policy import PPO, VMPO  # noqa: F401
 
-__all__ = ["PPO"]
+__all__ = ["PPO", "VMPO"]
