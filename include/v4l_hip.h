@@ -391,7 +391,8 @@ int v4l_trainer_sync_target(v4l_trainer* tr, void* stream);
 /* ---- V-MPO minibatch update (version 110): replaces VMPO.update_actor (torchrl/algo/on_policy/v_mpo.py:58-134) — the critic
  * step, the advantage statistics and both clip + Adam launches are the PPO phases above with clipped_value_loss = 0
  * (v_mpo.py:136-155, 173-182). One update = v4l_trainer_begin, then eagerly v4l_trainer_critic_grads, v4l_trainer_critic_step,
- * v4l_trainer_vmpo_actor_grads, v4l_trainer_actor_step (no hipGraph of a V-MPO update yet). Single process only. ---- */
+ * v4l_trainer_vmpo_actor_grads, v4l_trainer_actor_step — or, as one call, v4l_trainer_vmpo_update_next; v4l_trainer_vmpo_update_run
+ * runs a whole run of them as ONE hipGraph replay (version 111), like v4l_trainer_update_run for PPO. Single process only. ---- */
 typedef struct v4l_vmpo_hyper {
   double eta_eps;   /* v_mpo.py:20,27: 0.02 */
   double alpha_eps; /* v_mpo.py:21,31: 0.1  */
@@ -420,6 +421,25 @@ int v4l_trainer_vmpo_init(v4l_trainer* tr, const v4l_vmpo_hyper* vhp, void* bloc
  * mean and sigma (v_mpo.py:81-96). hp->world_size must be 1. */
 int v4l_trainer_vmpo_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* vstats_all_dev,
                                  void* stream);
+/* (version 111) The next V-MPO update of the run opened by v4l_trainer_begin: v4l_trainer_critic_grads, v4l_trainer_critic_step,
+ * the V-MPO actor stage above and v4l_trainer_actor_step (v_mpo.py:181-182), by the rules of v4l_trainer_update_next: with
+ * use_graph the first update of a configuration runs eagerly (it uploads the descriptor tables, those of the ceil(n / 2)-row
+ * passes too), later ones are one hipGraph replay each; the built-in profiler, a null stream or use_graph = 0 run eagerly.
+ * The library captures on `stream` itself and refuses a stream that is already capturing; under capture the target forward
+ * stays on `stream` (as in v4l_trainer_actor_grads: no forward, with its memset nodes, on a forked stream of a capture). V-MPO graphs have a key and handles of their own, apart from PPO's:
+ * the v4l_rollout, n and v4l_ppo_hyper bytes, the three nets' generations, the V-MPO block's address, vstats_all_dev and the
+ * stored v4l_vmpo_hyper; they are dropped wherever PPO's are (re-bind, destroy, other row / record addresses at begin, a key
+ * change), and a PPO update on the same trainer drops them (and the other way round). Same kernels, same arguments, same bits
+ * as the eager sequence. */
+int v4l_trainer_vmpo_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* vstats_all_dev,
+                                 int use_graph, void* stream);
+/* `count` such updates behind one v4l_trainer_begin; with use_graph, on a configuration that has run before, ONE hipGraph replay
+ * for all of them (captured by the first such call, re-captured when count changes). Otherwise update by update. */
+int v4l_trainer_vmpo_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* vstats_all_dev,
+                                int count, int use_graph, void* stream);
+/* V-MPO graphs instantiated and hipGraphLaunch calls made by the two entries above since the trainer was created (what tells a
+ * replay from an eager run with the same bits) */
+int v4l_trainer_vmpo_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays);
 /* eta, alpha and the state of their optimiser (V4L_VMPO_STATE doubles), read back (synchronises the stream) / written */
 int v4l_trainer_vmpo_state(v4l_trainer* tr, double* out, void* stream);
 int v4l_trainer_vmpo_set_state(v4l_trainer* tr, const double* in, void* stream);

@@ -155,6 +155,9 @@ _SIGS = {
   "v4l_trainer_vmpo_bytes": (C.c_int64, [_P, C.c_int]),
   "v4l_trainer_vmpo_init": (C.c_int, [_P, C.POINTER(VMPOHyper), _P, C.c_int, _P]),
   "v4l_trainer_vmpo_actor_grads": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), _P, _P]),
+  "v4l_trainer_vmpo_update_next": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), _P, C.c_int, _P]),
+  "v4l_trainer_vmpo_update_run": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), _P, C.c_int, C.c_int, _P]),
+  "v4l_trainer_vmpo_graph_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
   "v4l_trainer_vmpo_state": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
   "v4l_trainer_vmpo_set_state": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
   "v4l_vmpo_select": (C.c_int, [_P, _P, C.c_int, _P, _P]),

@@ -219,6 +219,9 @@ struct v4l_actor {
 };
 
 struct GraphKey { v4l_rollout ro; v4l_ppo_hyper hp; int n; int gen[3]; };
+// everything a captured V-MPO update bakes into its nodes beyond GraphKey: the V-MPO block (its owner moves it when the
+// minibatch grows), the V-MPO record array and the stored v4l_vmpo_hyper (compared bytewise: zero the key first)
+struct VmpoGraphKey { GraphKey base; const void* block; const float* vstats_all; v4l_vmpo_hyper vhp; };
 
 struct v4l_trainer {
   v4l_net *pf = nullptr, *vf = nullptr, *tpf = nullptr;
@@ -252,4 +255,11 @@ struct v4l_trainer {
   int* vmpo_sel = nullptr;
   int vmpo_n_max = 0;
   v4l_vmpo_hyper vmpo_hp = {};
+  // hipGraphs of a V-MPO update / of a run of them: a key and handles of their own, never PPO's (v4l_trainer_vmpo_update_next)
+  VmpoGraphKey vkey = {};
+  hipGraphExec_t vexec = nullptr;
+  hipGraphExec_t vexec_run = nullptr;
+  int vexec_run_count = 0;
+  bool vwarm = false;
+  int64_t vmpo_captures = 0, vmpo_replays = 0;  // graphs instantiated / hipGraphLaunch calls (v4l_trainer_vmpo_graph_counts)
 };

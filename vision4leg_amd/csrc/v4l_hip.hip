@@ -2649,7 +2649,7 @@ static int launch_vmpo_loss(hipStream_t s, const ActorArgs& aa, const VmpoArgs& 
 extern "C" {
 
 const char* v4l_last_error(void) { return v4l::last_error(); }
-int v4l_version(void) { return 110; }  // V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
+int v4l_version(void) { return 111; }  // V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
 int v4l_abi_sizeof(int which) {
   return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) :
          which == 4 ? (int)sizeof(v4l_vmpo_hyper) : -1;  // (3 stays unassigned)
@@ -3307,11 +3307,22 @@ int v4l_trainer_create(v4l_net* pf, v4l_net* vf, v4l_net* target_pf, v4l_trainer
   *out = t;
   return 0;
 }
-static void drop_graph(v4l_trainer* tr) {
+static void drop_ppo_graph(v4l_trainer* tr) {
   if (tr->gexec) { (void)hipGraphExecDestroy(tr->gexec); tr->gexec = nullptr; }
   if (tr->gexec_run) { (void)hipGraphExecDestroy(tr->gexec_run); tr->gexec_run = nullptr; }
   tr->gexec_run_count = 0;
   tr->warm = false;
+}
+static void drop_vmpo_graph(v4l_trainer* tr) {
+  if (tr->vexec) { (void)hipGraphExecDestroy(tr->vexec); tr->vexec = nullptr; }
+  if (tr->vexec_run) { (void)hipGraphExecDestroy(tr->vexec_run); tr->vexec_run = nullptr; }
+  tr->vexec_run_count = 0;
+  tr->vwarm = false;
+}
+// (PPO's graphs and V-MPO's: both bake the same addresses in, so whatever invalidates one invalidates the other)
+static void drop_graph(v4l_trainer* tr) {
+  drop_ppo_graph(tr);
+  drop_vmpo_graph(tr);
 }
 void v4l_trainer_destroy(v4l_trainer* tr) {
   if (tr) drop_graph(tr);
@@ -3674,15 +3685,22 @@ int v4l_trainer_vmpo_set_state(v4l_trainer* tr, const double* in, void* stream) 
               "v4l_trainer_vmpo_set_state: eta, alpha must be > 0, the second moments and the step count >= 0");
   return vmpo_write_state(tr, in, (hipStream_t)stream);
 }
-int v4l_trainer_vmpo_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* vstats_all_dev,
-                                 void* stream) {
+static int check_vmpo_args(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp) {
   int rc = check_update_args(tr, ro, n, hp);
   if (rc) return rc;
   V4L_REQUIRE(tr->vmpo != nullptr, "v4l_trainer_vmpo_actor_grads: no V-MPO state (v4l_trainer_vmpo_init)");
   V4L_REQUIRE(n <= tr->vmpo_n_max, "v4l_trainer_vmpo_actor_grads: n = %d is over the V-MPO block's n_max = %d", n, tr->vmpo_n_max);
   V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_vmpo_actor_grads: V-MPO runs in a single process");
+  return 0;
+}
+// The actor stage itself, eagerly or under THIS library's capture (v4l_trainer_vmpo_update_next / _update_run). Under capture the
+// target forward stays on the capturing stream, as in v4l_trainer_actor_grads: its launch sequence holds memset nodes
+// (hipMemsetAsync / hipMemset2DAsync of the forward's row buffers), and a capture with those on a forked side stream is the
+// pattern that crashes inside the runtime (see capturing() above; the captured weight-grad forks hold kernels only).
+static int vmpo_actor_stage(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* vstats_all_dev,
+                            void* stream) {
+  int rc;
   hipStream_t s = (hipStream_t)stream;
-  V4L_REQUIRE(!capturing(s), "v4l_trainer_vmpo_actor_grads: a V-MPO update is a sequence of eager launches (no stream capture)");
   v4l_net *pf = tr->pf, *tp = tr->tpf;
   const int m = (n + 1) / 2;  // idx.chunk(2)[0], v_mpo.py:67
   const int* sel = tr->vmpo_sel;
@@ -3692,7 +3710,7 @@ int v4l_trainer_vmpo_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, 
   float* ws_t = tr->ws + std::max(pf->layout(n).total, tr->vf->layout(n).total);
   // 2. the frozen target policy on those rows, next to the live policy's repack + forward (v4l_trainer_actor_grads' fork)
   hipStream_t s_tgt = s;
-  const bool par_tgt = tr->aux != nullptr;
+  const bool par_tgt = tr->aux != nullptr && !capturing(s);
   if (par_tgt) {
     V4L_HIP_CHECK(hipEventRecord(tr->ev_fork, s));
     V4L_HIP_CHECK(hipStreamWaitEvent(tr->aux, tr->ev_fork, 0));
@@ -3728,6 +3746,15 @@ int v4l_trainer_vmpo_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, 
   }
   PhaseScope ps("pf.bwd");  // 6.
   return v4l_net_backward(pf, ro->state_dev, ro->image_dev, sel, m, tr->ws, tr->g_pf, stream);
+}
+int v4l_trainer_vmpo_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* vstats_all_dev,
+                                 void* stream) {
+  int rc = check_vmpo_args(tr, ro, n, hp);
+  if (rc) return rc;
+  // (a caller's capture is refused: the captured V-MPO update is v4l_trainer_vmpo_update_next's, which keys and owns its graph)
+  V4L_REQUIRE(!capturing((hipStream_t)stream),
+              "v4l_trainer_vmpo_actor_grads: a V-MPO update is a sequence of eager launches (no stream capture)");
+  return vmpo_actor_stage(tr, ro, n, hp, vstats_all_dev, stream);
 }
 
 
@@ -3890,6 +3917,7 @@ int v4l_trainer_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const
   int rc = check_update_args(tr, ro, n, hp);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
+  drop_vmpo_graph(tr);  // (a PPO update on a V-MPO trainer runs the policy's pass over n rows: other descriptor tables)
   if (!use_graph || g_prof || s == nullptr) return run_update(tr, ro, n, hp, stream);
   // the captured launch sequence is specific to (rollout pointers, n, hyper-parameters)
   GraphKey key;
@@ -3956,6 +3984,96 @@ int v4l_trainer_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const 
     V4L_TRACE("update run: instantiated");
   }
   V4L_HIP_CHECK(hipGraphLaunch(tr->gexec_run, s));
+  return 0;
+}
+
+// ---- V-MPO updates: v4l_trainer_update_next / _update_run's rules with the V-MPO actor stage, graphs and key of their own
+static int run_vmpo_update(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* vstats_all_dev,
+                           void* stream) {
+  int rc;  // v_mpo.py:181-182: update_critic, then update_actor
+  if ((rc = v4l_trainer_critic_grads(tr, ro, n, hp, stream))) return rc;
+  if ((rc = v4l_trainer_critic_step(tr, hp, stream))) return rc;
+  if ((rc = vmpo_actor_stage(tr, ro, n, hp, vstats_all_dev, stream))) return rc;
+  return v4l_trainer_actor_step(tr, hp, stream);
+}
+static void vmpo_graph_key(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, const float* vstats_all_dev,
+                           VmpoGraphKey* key) {
+  memset(key, 0, sizeof(*key));
+  key->base.ro = *ro; memcpy(&key->base.hp, hp, sizeof(*hp)); key->base.n = n;  // (bytewise: v4l_ppo_hyper ends in padding)
+  key->base.gen[0] = tr->pf->gen; key->base.gen[1] = tr->vf->gen; key->base.gen[2] = tr->tpf->gen;
+  key->block = tr->vmpo; key->vstats_all = vstats_all_dev;
+  memcpy(&key->vhp, &tr->vmpo_hp, sizeof(tr->vmpo_hp));
+}
+// Captures `count` V-MPO updates on s into *exec
+static int capture_vmpo(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* vstats_all_dev, int count,
+                        hipStream_t s, hipGraphExec_t* exec) {
+  hipGraph_t graph = nullptr;
+  int rc = 0;
+  V4L_TRACE("vmpo update: begin capture of %d update(s)", count);
+  V4L_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  for (int u = 0; u < count && !rc; ++u) rc = run_vmpo_update(tr, ro, n, hp, vstats_all_dev, (void*)s);
+  const hipError_t e = hipStreamEndCapture(s, &graph);
+  if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+  V4L_HIP_CHECK(e);
+  V4L_HIP_CHECK(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
+  V4L_HIP_CHECK(hipGraphDestroy(graph));
+  ++tr->vmpo_captures;
+  V4L_TRACE("vmpo update: instantiated");
+  return 0;
+}
+int v4l_trainer_vmpo_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* vstats_all_dev,
+                                 int use_graph, void* stream) {
+  int rc = check_vmpo_args(tr, ro, n, hp);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  V4L_REQUIRE(!capturing(s), "v4l_trainer_vmpo_update_next: called under a caller's stream capture (use_graph = 1 captures itself)");
+  drop_ppo_graph(tr);  // (the policy's pass runs over ceil(n / 2) rows here: other descriptor tables than a PPO update's)
+  if (!use_graph || g_prof || s == nullptr) return run_vmpo_update(tr, ro, n, hp, vstats_all_dev, stream);
+  VmpoGraphKey key;
+  vmpo_graph_key(tr, ro, n, hp, vstats_all_dev, &key);
+  if (memcmp(&key, &tr->vkey, sizeof(key)) != 0) { drop_vmpo_graph(tr); tr->vkey = key; }
+  if (!tr->vwarm) {  // first update of a configuration runs eagerly: it uploads the descriptor tables (the m-row passes' too)
+    tr->vwarm = true;
+    return run_vmpo_update(tr, ro, n, hp, vstats_all_dev, stream);
+  }
+  if (tr->vexec == nullptr && (rc = capture_vmpo(tr, ro, n, hp, vstats_all_dev, 1, s, &tr->vexec))) return rc;
+  V4L_HIP_CHECK(hipGraphLaunch(tr->vexec, s));
+  ++tr->vmpo_replays;
+  return 0;
+}
+int v4l_trainer_vmpo_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* vstats_all_dev,
+                                int count, int use_graph, void* stream) {
+  int rc = check_vmpo_args(tr, ro, n, hp);
+  if (rc) return rc;
+  V4L_REQUIRE(count >= 1, "v4l_trainer_vmpo_update_run: count must be >= 1");
+  hipStream_t s = (hipStream_t)stream;
+  V4L_REQUIRE(!capturing(s), "v4l_trainer_vmpo_update_run: called under a caller's stream capture (use_graph = 1 captures itself)");
+  VmpoGraphKey key;
+  vmpo_graph_key(tr, ro, n, hp, vstats_all_dev, &key);
+  const bool same = memcmp(&key, &tr->vkey, sizeof(key)) == 0;
+  if (!use_graph || g_prof || s == nullptr || !same || !tr->vwarm) {
+    // no graph, or a configuration this trainer has not run yet: update by update (the first one eagerly, then single-update
+    // replays); the next call captures the whole run
+    for (int u = 0; u < count; ++u)
+      if ((rc = v4l_trainer_vmpo_update_next(tr, ro, n, hp, vstats_all_dev, use_graph, stream))) return rc;
+    return 0;
+  }
+  if (tr->vexec_run != nullptr && tr->vexec_run_count != count) {
+    (void)hipGraphExecDestroy(tr->vexec_run);
+    tr->vexec_run = nullptr;
+  }
+  if (tr->vexec_run == nullptr) {
+    if ((rc = capture_vmpo(tr, ro, n, hp, vstats_all_dev, count, s, &tr->vexec_run))) return rc;
+    tr->vexec_run_count = count;
+  }
+  V4L_HIP_CHECK(hipGraphLaunch(tr->vexec_run, s));
+  ++tr->vmpo_replays;
+  return 0;
+}
+int v4l_trainer_vmpo_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays) {
+  V4L_REQUIRE(tr && captures && replays, "v4l_trainer_vmpo_graph_counts: null argument");
+  *captures = tr->vmpo_captures;
+  *replays = tr->vmpo_replays;
   return 0;
 }
 

@@ -625,13 +625,35 @@ class HipTrainer:
     check(self.L.v4l_trainer_vmpo_actor_grads(self.h, C.byref(ro), n, C.byref(self.hp), _ptr(vstats_all), _stream()),
           "v4l_trainer_vmpo_actor_grads")
 
-  def vmpo_update_next(self, ro, n, vstats_all=None):
-    """The next V-MPO minibatch update of the run begin() opened: five eager phases in the order of v_mpo.py:181-182."""
+  def vmpo_update_next(self, ro, n, vstats_all=None, graph=False):
+    """The next V-MPO minibatch update of the run begin() opened (v4l_trainer_vmpo_update_next): critic_grads, critic_step, the
+    V-MPO actor stage and actor_step in the order of v_mpo.py:181-182. graph=True: one hipGraph replay once the configuration
+    has run; graph=False: eager launches."""
+    if self._vmpo is None:
+      raise RuntimeError("vision4leg_amd: vmpo_init() first")
     self._pre(n)
-    self.critic_grads(ro, n)
-    self.critic_step()
-    self.vmpo_actor_grads(ro, n, vstats_all)
-    self.actor_step()
+    check(self.L.v4l_trainer_vmpo_update_next(self.h, C.byref(ro), n, C.byref(self.hp), _ptr(vstats_all), int(graph), _stream()),
+          "v4l_trainer_vmpo_update_next")
+    self._count(1)
+    self._after_steps()
+
+  def vmpo_update_run(self, ro, n, count, vstats_all, graph=True):
+    """The next `count` V-MPO updates behind one begin(): with graph=True ONE hipGraph replay for all of them
+    (v4l_trainer_vmpo_update_run). Keep the row-index, record and vstats_all tensors at one address from run to run: the graph
+    is keyed on them."""
+    if self._vmpo is None:
+      raise RuntimeError("vision4leg_amd: vmpo_init() first")
+    self._pre(n)
+    check(self.L.v4l_trainer_vmpo_update_run(self.h, C.byref(ro), n, C.byref(self.hp), _ptr(vstats_all), int(count), int(graph),
+                                             _stream()), "v4l_trainer_vmpo_update_run")
+    self._count(int(count))
+    self._after_steps()
+
+  def vmpo_graph_counts(self):
+    """-> (V-MPO graphs instantiated, V-MPO graph replays launched) since this trainer was created."""
+    cap, rep = C.c_int64(0), C.c_int64(0)
+    check(self.L.v4l_trainer_vmpo_graph_counts(self.h, C.byref(cap), C.byref(rep)), "v4l_trainer_vmpo_graph_counts")
+    return cap.value, rep.value
 
 
 def vmpo_select(adv, rowidx, n):

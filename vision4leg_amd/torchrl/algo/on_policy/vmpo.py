@@ -6,7 +6,8 @@ What differs is the actor stage of a minibatch update (v_mpo.py:58-134): the bet
 advantage is chosen on the device (vmpo_select_kernel), the live and the frozen target policy run on those rows, and one
 single-block launch (vmpo_loss_kernel) forms the softmax-weighted log-prob + alpha KL loss, its gradients, the statistics and
 the Adam step of the two learnable scalars eta and alpha. The critic step, the clip + Adam launches and the advantage statistics
-are PPO's with clipped_value_loss=False. One update is a sequence of eager launches (no hipGraph yet); with a
+are PPO's with clipped_value_loss=False. All updates of an epoch are ONE hipGraph replay on the trainer's stream, like PPO's
+(V4L_EPOCH_GRAPH=0: one replay per update; V4L_GRAPH=0: eager launches; update(batch): the single-update replay); with a
 DeviceOnPolicyReplayBuffer the records of all updates of an epoch come back in one device-to-host copy.
 
 Not supported, refused at construction: data parallel (world_size > 1, V4L_FORCE_DP_PHASES), skip_nonfinite_steps,
@@ -95,22 +96,40 @@ class VMPO(PPO):
                     infos = self.update(batch)
                     self.logger.add_update_info(infos)
 
-    def _records(self, U):
-        """One allocation for both record arrays of U updates: [U][V4L_STATS] PPO records, then [U][V4L_VMPO_STATS]."""
-        rec = torch.zeros(U * (_lib.V4L_STATS + _lib.V4L_VMPO_STATS), dtype=torch.float32, device=self.device)
-        return rec, rec[:U * _lib.V4L_STATS].view(U, _lib.V4L_STATS), rec[U * _lib.V4L_STATS:].view(U, _lib.V4L_VMPO_STATS)
+    def _buffers(self, rowidx, U):
+        """The row-index tensor and both record arrays of a run of U updates — one allocation: [U][V4L_STATS] PPO records, then
+        [U][V4L_VMPO_STATS] — at one address from run to run (the captured graphs are keyed on them): reallocated only when the
+        shape changes."""
+        shape = (U, None if rowidx is None else tuple(rowidx.shape))
+        if getattr(self, "_vbuf_shape", None) != shape:
+            self._vbuf_shape = shape
+            self._vrowidx_buf = None if rowidx is None else torch.empty_like(rowidx)
+            self._vrec_buf = torch.zeros(U * (_lib.V4L_STATS + _lib.V4L_VMPO_STATS), dtype=torch.float32, device=self.device)
+            self._vpstats_buf = self._vrec_buf[:U * _lib.V4L_STATS].view(U, _lib.V4L_STATS)
+            self._vstats_buf = self._vrec_buf[U * _lib.V4L_STATS:].view(U, _lib.V4L_VMPO_STATS)
+        if rowidx is not None:
+            self._vrowidx_buf.copy_(rowidx)
+        return self._vrowidx_buf, self._vrec_buf, self._vpstats_buf, self._vstats_buf
 
     def _run(self, ro, rowidx, n, U, what):
-        """U eager updates on rows rowidx[u] (None: rows 0 .. n-1), then ONE device-to-host copy of both record arrays and the
-        host's checks. -> list of U info dicts."""
+        """U updates on rows rowidx[u] (None: rows 0 .. n-1) on the trainer's stream, then ONE device-to-host copy of both record
+        arrays and the host's checks. -> list of U info dicts. The whole run is ONE hipGraph replay (one replay per update with
+        V4L_EPOCH_GRAPH=0, eager launches with V4L_GRAPH=0), by PPO.run_updates' switches."""
         tr = self.trainer
-        rec, stats, vstats = self._records(U)
-        tr._pre(n)
-        tr.begin(rowidx, stats, self.pf_optimizer.lr, self.vf_optimizer.lr)
-        for _ in range(U):
-            self.training_update_num += 1
-            tr.vmpo_update_next(ro, n, vstats)
-        host = rec.cpu().numpy()  # the only device->host sync of the run
+        rows, rec, stats, vstats = self._buffers(rowidx, U)
+        cur = torch.cuda.current_stream(self.device)
+        tr.stream.wait_stream(cur)
+        with torch.cuda.stream(tr.stream):
+            tr._pre(n)
+            tr.begin(rows, stats, self.pf_optimizer.lr, self.vf_optimizer.lr)
+            self.training_update_num += U
+            if self.use_graph and os.environ.get("V4L_EPOCH_GRAPH", "1") != "0":
+                tr.vmpo_update_run(ro, n, U, vstats, graph=True)
+            else:
+                for _ in range(U):
+                    tr.vmpo_update_next(ro, n, vstats, graph=self.use_graph)
+            host = rec.cpu().numpy()  # the only device->host sync of the run
+        cur.wait_stream(tr.stream)
         hs = host[:U * _lib.V4L_STATS].reshape(U, _lib.V4L_STATS)
         hv = host[U * _lib.V4L_STATS:].reshape(U, _lib.V4L_VMPO_STATS)
         _check_update_records(hs, None, False, what)
@@ -153,9 +172,13 @@ class VMPO(PPO):
             if self._stage is None or self._stage[0].shape[0] != n:
                 self._stage = net.alloc_rollout(n, dev)
             net.ingest(obs, self._stage[0], self._stage[1])
-            acts = up(batch["acts"]).reshape(n, -1)
-            advs = up(batch["advs"]).reshape(n)
-            rets = up(batch["estimate_returns"]).reshape(n)
-            vals = up(batch["values"]).reshape(n)
-            ro = HipTrainer.rollout(self._stage[0], self._stage[1], acts, advs, rets, vals)
+            # the rollout arrays keep their addresses from call to call (the single-update graph is keyed on them)
+            new = {"acts": up(batch["acts"]).reshape(n, -1), "advs": up(batch["advs"]).reshape(n),
+                   "rets": up(batch["estimate_returns"]).reshape(n), "vals": up(batch["values"]).reshape(n)}
+            held = getattr(self, "_vstage", None)
+            if held is None or any(held[k].shape != v.shape for k, v in new.items()):
+                held = self._vstage = {k: torch.empty_like(v) for k, v in new.items()}
+            for k, v in new.items():
+                held[k].copy_(v)
+            ro = HipTrainer.rollout(self._stage[0], self._stage[1], held["acts"], held["advs"], held["rets"], held["vals"])
             return self._run(ro, None, n, 1, lambda u: "minibatch update %d" % self.training_update_num)[0]
