@@ -447,6 +447,45 @@ int v4l_trainer_vmpo_set_state(v4l_trainer* tr, const double* in, void* stream);
  * r-th largest adv_dev[slot], r < ceil(n / 2); ties to the earlier i, NaN after every number. n >= 1. */
 int v4l_vmpo_select(const float* adv_dev, const int* rowidx_dev, int n, int* sel_dev, void* stream);
 
+/* ---- A2C minibatch update (version 112): replaces A2C.update (torchrl/algo/on_policy/a2c.py:46-107) for state-MLP nets
+ * (V4L_NET_MLP) whose policy and critic share no parameter — the only pairs the reference's A2C can run: it evaluates vf(obs)
+ * before pf_optimizer.step() and backpropagates vf_loss after it (a2c.py:76-85), which torch refuses for common parameters.
+ * With disjoint parameter sets the two steps are independent, so an update keeps the critic-first order of the PPO update:
+ * v4l_trainer_begin, then v4l_trainer_a2c_critic_grads, v4l_trainer_critic_step, v4l_trainer_a2c_actor_grads,
+ * v4l_trainer_actor_step. No ratio, no target policy (the trainer's third net is never run), max_grad_norm is the caller's
+ * v4l_ppo_hyper's (a2c.py:81,86: 0.5), entropy_coeff too. Single process only. ---- */
+#define V4L_A2C_STATS 16 /* floats per update in the A2C record; [0..11] = the 12 keys of a2c.py:89-105 in that order:
+                            Training/policy_loss, Training/vf_loss, v_pred/mean, std, max, min, std/mean, std, max, min, ent,
+                            log_prob; the rest stays as the caller cleared it */
+/* a2c.py:76-77,84-85: the row selection and advantage statistics of v4l_trainer_critic_grads' opening launch, the critic's
+ * forward, nn.MSELoss (critic_loss_kernel's arithmetic) with v_pred/mean, std (unbiased over n), max, min (a2c.py:92-95), and the
+ * critic's backward. astats_all_dev: [U][V4L_A2C_STATS] records of the run opened by v4l_trainer_begin (row = the update's
+ * index), not NULL. Fills the PPO record's advantage statistics and vf_loss. hp->world_size must be 1. */
+int v4l_trainer_a2c_critic_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,
+                                 void* stream);
+/* a2c.py:61-74,79-80: the policy's forward on the update's rows, the A2C loss launch — policy_loss = mean(-log_prob * an)
+ * - entropy_coeff * ent with an = (a - mean) / (std + 1e-5) from the minibatch statistics (a2c.py:68), its gradients w.r.t. mean
+ * and log sigma, std/mean, std (unbiased over n * A), max, min, ent and log_prob (a2c.py:97-105) — and the policy's backward.
+ * Fills the PPO record's policy_loss and logprob/mean; the other PPO slots stay at the cleared 0. ro->logp_old_dev and
+ * ro->values_dev are ignored. v4l_trainer_actor_step follows (it closes the update). */
+int v4l_trainer_a2c_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,
+                                void* stream);
+/* The next A2C update of the run opened by v4l_trainer_begin (a2c.py:46-107), by the rules of v4l_trainer_update_next: with
+ * use_graph the first update of a configuration runs eagerly, later ones are one hipGraph replay each; the built-in profiler, a
+ * null stream or use_graph = 0 run eagerly. The library captures on `stream` itself and refuses a stream that is already
+ * capturing. A2C graphs have a key (the v4l_rollout, n and v4l_ppo_hyper bytes, the nets' generations, astats_all_dev) and
+ * handles of their own, apart from PPO's and V-MPO's; they are dropped wherever those are, and an update of one kind on a
+ * trainer drops the graphs of the other kinds. Same kernels, same arguments, same bits as the eager sequence. */
+int v4l_trainer_a2c_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,
+                                int use_graph, void* stream);
+/* `count` such updates behind one v4l_trainer_begin — a2c.py's epoch is one pass over the samples (on_rl_algo.py:36-41); with
+ * use_graph, on a configuration that has run before, ONE hipGraph replay for all of them (captured by the first such call,
+ * re-captured when count changes). Otherwise update by update. */
+int v4l_trainer_a2c_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,
+                               int count, int use_graph, void* stream);
+/* A2C graphs instantiated and hipGraphLaunch calls made by the two entries above since the trainer was created */
+int v4l_trainer_a2c_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays);
+
 /* ---- data parallel: one process per GPU, every rank owns an env shard and its own rollout; gradients are
  * summed with ONE in-place RCCL all-reduce per optimiser step on the flat gradient buffer. The reference has no
  * counterpart (single process); the exchange sits where `vf_loss.backward()` / `policy_loss.backward()` end

@@ -1221,6 +1221,128 @@ __global__ __launch_bounds__(1024) void vmpo_loss_kernel(ActorArgs p, VmpoArgs q
 __global__ void vmpo_state_set_kernel(VmpoState* vs, double eta, double alpha, double m0, double m1, double v0, double v1, long long step) {
   vs->eta = eta; vs->alpha = alpha; vs->m[0] = m0; vs->m[1] = m1; vs->v[0] = v0; vs->v[1] = v1; vs->step = step;
 }
+
+// --------------------------------------------------------------------------------- A2C (torchrl/algo/on_policy/a2c.py)
+// V4L_A2C_STATS floats per update, next to the PPO record: the 12 logger scalars of A2C.update in the reference's order
+// (a2c.py:89-105). The critic's loss launch files AST_VF_LOSS .. AST_VP_MIN, the policy's the rest, both in row ctl->upd_index.
+enum { AST_PI_LOSS = 0, AST_VF_LOSS, AST_VP_MEAN, AST_VP_STD, AST_VP_MAX, AST_VP_MIN, AST_SD_MEAN, AST_SD_STD, AST_SD_MAX, AST_SD_MIN,
+       AST_ENT, AST_LOGP, AST_SIZE = V4L_A2C_STATS };
+static_assert(AST_LOGP < AST_SIZE, "the A2C record holds the 12 keys");
+// nn.MSELoss()(vf(obs), est_rets) and its gradient (a2c.py:76-77): critic_loss_body with clipped = 0, then values.mean(), .std()
+// (Bessel), .max(), .min() of the critic's output column (a2c.py:92-95). Single block.
+__global__ __launch_bounds__(1024) void a2c_critic_loss_kernel(const float* __restrict__ values, const float* __restrict__ ret,
+                                                              const int* __restrict__ rowidx, int n, float inv_n,
+                                                              float* __restrict__ dvalues, float* __restrict__ st, float gscale,
+                                                              const UpdCtl* __restrict__ ctl, float* __restrict__ ast_all) {
+  critic_loss_body(values, ret, nullptr, rowidx, n, inv_n, 0, 0.f, dvalues, st, gscale);
+  double s = 0.0; float mx = -INFINITY, mn = INFINITY;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const float v = values[(int64_t)i * OUT_LD];
+    s += v; mx = fmaxf(mx, v); mn = fminf(mn, v);
+  }
+  const Red4 r = block_red4(s, 0.0, mx, mn);
+  const double mean = r.s / n;
+  double q = 0.0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const double v = values[(int64_t)i * OUT_LD];
+    q += (v - mean) * (v - mean);
+  }
+  const Red4 r2 = block_red4(q, 0.0, 0.f, 0.f);
+  if (threadIdx.x == 0) {
+    float* ast = ast_all + (int64_t)ctl->upd_index * AST_SIZE;
+    ast[AST_VF_LOSS] = st[ST_VF_LOSS];  // (this thread wrote it in critic_loss_body)
+    ast[AST_VP_MEAN] = (float)mean;
+    ast[AST_VP_STD] = (float)sqrt(r2.s / (double)(n - 1));
+    ast[AST_VP_MAX] = r.mx; ast[AST_VP_MIN] = r.mn;
+  }
+}
+// A2C.update's policy loss (a2c.py:61-74) and its gradient w.r.t. the policy mean [n][OUT_LD] and log sigma [A]; single block,
+// the sibling of actor_loss_kernel without ratio, clip or target policy (p.tmean, p.tlogstd, p.logp_old, p.clip unused).
+//   policy_loss = mean_i(-logp_i an_i) - ent_coef ent        an: the advantage normalised with the minibatch statistics in p.st
+//   ent = sum_a (0.5 + 0.5 log(2 pi) + log sigma_a): the plain Normal's also for TanhNormal policies (distribution.py:79-80),
+//   the same for every row, so ent.mean() is that sum.
+// std/*: over the [n][A] expanded tensor pf.update returns (continuous_policy.py:252-253): every column holds one sigma n times.
+// Fills ST_PI_LOSS and ST_LP_MEAN of the PPO record (the closing Adam launch's non-finite count reads them); the record's other
+// policy slots stay at the cleared 0.
+template <bool TANH, int CAP>
+__global__ __launch_bounds__(1024) void a2c_loss_kernel(ActorArgs p, const UpdCtl* __restrict__ ctl, float* __restrict__ ast_all) {
+  __shared__ float sdl[16][CAP];
+  const int n = p.n, A = p.A;
+  const ActorDimsT<CAP> D = actor_dims<CAP>(p);
+  float dl[CAP];
+#pragma unroll
+  for (int a = 0; a < CAP; ++a) dl[a] = 0.f;
+  const float amean = p.st[ST_ADV_MEAN], astd = p.st[ST_ADV_STD];
+  double s_lp = 0.0, s_loss = 0.0;
+  int sat = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int slot = p.rowidx ? p.rowidx[i] : i;
+    const float an = (p.adv[slot] - amean) / (astd + 1e-5f);
+    const float dlp = -p.inv_n * an;  // d(mean(-logp an)) / d(logp_i)
+    float mu[CAP], dmr[CAP];
+    actor_load_row(p.mean + (int64_t)i * OUT_LD, mu);
+    float lp = 0.f;
+#pragma unroll
+    for (int a = 0; a < CAP; ++a) {
+      dmr[a] = 0.f;
+      if (a < A) {
+        const float act = p.acts[(int64_t)slot * A + a];
+        const float x = TANH ? tanh_pre(act) : act;
+        const float corr = TANH ? tanh_corr(act) : 0.f;
+        const float d = x - mu[a];
+        const float var = D.sg[a] * D.sg[a];
+        lp += -(d * d) / (2.f * var) - D.lsg[a] - HALF_LOG_2PI - corr;
+        dmr[a] = grad_out(dlp * (d / var), p.gscale, sat);
+        dl[a] += dlp * (d * d / var - 1.f);
+      }
+    }
+    actor_store_dmean(p.dmean + (int64_t)i * OUT_LD, dmr, true);
+    s_loss += (double)(-lp * an);
+    s_lp += lp;
+  }
+  const Red4 r = block_red4(s_loss, s_lp, 0.f, 0.f);
+  const Red4 r2 = block_red4((double)sat, 0.0, 0.f, 0.f);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int a = 0; a < CAP; ++a) {
+    const float v = wave_sum(dl[a]);
+    if (lane == 0) sdl[w][a] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < A) {
+    const int a = threadIdx.x;
+    const float raw = p.logstd[a];
+    float g = 0.f;
+    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) g += sdl[k][a];
+    g += -p.ent_coef * p.inv_n * (float)n;  // the entropy term, as in actor_loss_body
+    p.dlogstd[a] = (raw >= LOG_SIG_MIN && raw <= LOG_SIG_MAX) ? g : 0.f;  // the clamp of continuous_policy.py:486-492 passes no gradient outside
+  }
+  if (threadIdx.x == 0) {
+    float* st = p.st;
+    const double lpm = r.s2 / n;
+    const float loss = (float)(r.s / n - (double)p.ent_coef * D.ent);
+    st[ST_PI_LOSS] = loss;
+    st[ST_LP_MEAN] = (float)lpm;
+    if (p.gscale != 1.f) st[ST_F16_SAT] += (float)r2.s;
+    double m = 0.0; float mx = -INFINITY, mn = INFINITY;
+#pragma unroll
+    for (int a = 0; a < CAP; ++a)
+      if (a < A) { m += D.sg[a]; mx = fmaxf(mx, D.sg[a]); mn = fminf(mn, D.sg[a]); }
+    m /= A;
+    double q = 0.0;
+#pragma unroll
+    for (int a = 0; a < CAP; ++a)
+      if (a < A) q += (D.sg[a] - m) * (D.sg[a] - m);
+    const double cnt = (double)n * A;  // (n >= 2: never one element)
+    float* ast = ast_all + (int64_t)ctl->upd_index * AST_SIZE;
+    ast[AST_PI_LOSS] = loss;
+    ast[AST_SD_MEAN] = (float)m;
+    ast[AST_SD_STD] = (float)sqrt((double)n * q / (cnt - 1.0));
+    ast[AST_SD_MAX] = mx; ast[AST_SD_MIN] = mn;
+    ast[AST_ENT] = D.ent;
+    ast[AST_LOGP] = (float)lpm;
+  }
+}
 #pragma clang fp contract(fast)
 
 // --------------------------------------------------------------------------------- weight packing

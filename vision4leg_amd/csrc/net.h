@@ -222,6 +222,8 @@ struct GraphKey { v4l_rollout ro; v4l_ppo_hyper hp; int n; int gen[3]; };
 // everything a captured V-MPO update bakes into its nodes beyond GraphKey: the V-MPO block (its owner moves it when the
 // minibatch grows), the V-MPO record array and the stored v4l_vmpo_hyper (compared bytewise: zero the key first)
 struct VmpoGraphKey { GraphKey base; const void* block; const float* vstats_all; v4l_vmpo_hyper vhp; };
+// a captured A2C update bakes in GraphKey's fields and the A2C record array (compared bytewise: zero the key first)
+struct A2cGraphKey { GraphKey base; const float* astats_all; };
 
 struct v4l_trainer {
   v4l_net *pf = nullptr, *vf = nullptr, *tpf = nullptr;
@@ -262,4 +264,11 @@ struct v4l_trainer {
   int vexec_run_count = 0;
   bool vwarm = false;
   int64_t vmpo_captures = 0, vmpo_replays = 0;  // graphs instantiated / hipGraphLaunch calls (v4l_trainer_vmpo_graph_counts)
+  // hipGraphs of an A2C update / of a run of them: a key and handles of their own, never PPO's or V-MPO's (v4l_trainer_a2c_update_next)
+  A2cGraphKey akey = {};
+  hipGraphExec_t aexec = nullptr;
+  hipGraphExec_t aexec_run = nullptr;
+  int aexec_run_count = 0;
+  bool awarm = false;
+  int64_t a2c_captures = 0, a2c_replays = 0;  // graphs instantiated / hipGraphLaunch calls (v4l_trainer_a2c_graph_counts)
 };

@@ -2645,11 +2645,20 @@ static int launch_vmpo_loss(hipStream_t s, const ActorArgs& aa, const VmpoArgs& 
   return 0;
 }
 
+// A2C: the policy's single-block loss launch (csrc/elem.h)
+template <int CAP>
+static int launch_a2c_loss(hipStream_t s, const ActorArgs& aa, const UpdCtl* ctl, float* ast_all, dim3 blk) {
+  if (aa.tanh_action) V4L_KLAUNCH("a2c_loss", 0, s, (a2c_loss_kernel<true, CAP>), dim3(1), blk, 0, s, aa, ctl, ast_all);
+  else V4L_KLAUNCH("a2c_loss", 0, s, (a2c_loss_kernel<false, CAP>), dim3(1), blk, 0, s, aa, ctl, ast_all);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 extern "C" {
 
 const char* v4l_last_error(void) { return v4l::last_error(); }
-int v4l_version(void) { return 111; }  // V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
+int v4l_version(void) { return 112; }  // A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
 int v4l_abi_sizeof(int which) {
   return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) :
          which == 4 ? (int)sizeof(v4l_vmpo_hyper) : -1;  // (3 stays unassigned)
@@ -3320,9 +3329,16 @@ static void drop_vmpo_graph(v4l_trainer* tr) {
   tr->vwarm = false;
 }
 // (PPO's graphs and V-MPO's: both bake the same addresses in, so whatever invalidates one invalidates the other)
+static void drop_a2c_graph(v4l_trainer* tr) {
+  if (tr->aexec) { (void)hipGraphExecDestroy(tr->aexec); tr->aexec = nullptr; }
+  if (tr->aexec_run) { (void)hipGraphExecDestroy(tr->aexec_run); tr->aexec_run = nullptr; }
+  tr->aexec_run_count = 0;
+  tr->awarm = false;
+}
 static void drop_graph(v4l_trainer* tr) {
   drop_ppo_graph(tr);
   drop_vmpo_graph(tr);
+  drop_a2c_graph(tr);
 }
 void v4l_trainer_destroy(v4l_trainer* tr) {
   if (tr) drop_graph(tr);
@@ -3918,6 +3934,7 @@ int v4l_trainer_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   drop_vmpo_graph(tr);  // (a PPO update on a V-MPO trainer runs the policy's pass over n rows: other descriptor tables)
+  drop_a2c_graph(tr);
   if (!use_graph || g_prof || s == nullptr) return run_update(tr, ro, n, hp, stream);
   // the captured launch sequence is specific to (rollout pointers, n, hyper-parameters)
   GraphKey key;
@@ -4028,6 +4045,7 @@ int v4l_trainer_vmpo_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, 
   hipStream_t s = (hipStream_t)stream;
   V4L_REQUIRE(!capturing(s), "v4l_trainer_vmpo_update_next: called under a caller's stream capture (use_graph = 1 captures itself)");
   drop_ppo_graph(tr);  // (the policy's pass runs over ceil(n / 2) rows here: other descriptor tables than a PPO update's)
+  drop_a2c_graph(tr);
   if (!use_graph || g_prof || s == nullptr) return run_vmpo_update(tr, ro, n, hp, vstats_all_dev, stream);
   VmpoGraphKey key;
   vmpo_graph_key(tr, ro, n, hp, vstats_all_dev, &key);
@@ -4074,6 +4092,176 @@ int v4l_trainer_vmpo_graph_counts(const v4l_trainer* tr, int64_t* captures, int6
   V4L_REQUIRE(tr && captures && replays, "v4l_trainer_vmpo_graph_counts: null argument");
   *captures = tr->vmpo_captures;
   *replays = tr->vmpo_replays;
+  return 0;
+}
+
+// ---- A2C (torchrl/algo/on_policy/a2c.py:46-107) on state-MLP nets: the PPO update's opening launch, forwards, backwards and
+// clip + Adam launches around two loss launches of its own
+static int check_a2c_args(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, const float* astats_all_dev) {
+  int rc = check_update_args(tr, ro, n, hp);
+  if (rc) return rc;
+  V4L_REQUIRE(astats_all_dev != nullptr, "v4l_trainer_a2c: the A2C record array is missing");
+  V4L_REQUIRE(tr->pf->cfg.kind == V4L_NET_MLP && tr->vf->cfg.kind == V4L_NET_MLP,
+              "v4l_trainer_a2c: A2C runs state-MLP nets (V4L_NET_MLP) only: the reference's A2C raises on a shared encoder");
+  V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_a2c: A2C runs in a single process");
+  V4L_REQUIRE(tr->skip_all == nullptr, "v4l_trainer_a2c: no skipping of non-finite steps (v4l_trainer_begin_guarded) in an A2C run");
+  return 0;
+}
+// a2c.py:76-77, 84-85 (values = vf(obs), vf_loss, vf_loss.backward()): v4l_trainer_critic_grads' launches for a state-MLP net with
+// the A2C critic loss in critic_loss_kernel's place
+static int a2c_critic_stage(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev, void* stream) {
+  int rc;
+  hipStream_t s = (hipStream_t)stream;
+  v4l_net* vf = tr->vf;
+  float* st = tr->stats_cur;
+  const int* rowidx = tr->rowidx_cur;
+  g_op = "ctl";
+  if ((rc = by_compute(vf->cfg.compute, [&](auto tag) -> int {
+        typedef typename decltype(tag)::type T;
+        V4L_KLAUNCH("begin_pack", 0, s, begin_pack_kernel<T>, dim3((unsigned)vf->pack_blocks + 1), dim3(256), 0, s, tr->ctl, tr->rowidx_all, n,
+                    tr->rowidx_cur, st, ro->advs_dev, vf->d_packs, (int)vf->packs.size(), (T*)vf->packed);
+        V4L_LAUNCH_CHECK();
+        return 0;
+      })))
+    return rc;
+  { PhaseScope ps("vf.fwd");
+  if ((rc = v4l_net_forward(vf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, 1, stream))) return rc; }
+  const Layout L = vf->layout(n);
+  g_op = "loss";
+  const dim3 blk(n >= 512 ? 1024 : 256);
+  V4L_KLAUNCH("a2c_critic_loss", 0, s, a2c_critic_loss_kernel, dim3(1), blk, 0, s, tr->ws + L.out, ro->rets_dev, rowidx, n, 1.f / (float)n,
+              tr->ws + L.dout, st, v4l_net_grad_scale(vf, n), (const UpdCtl*)tr->ctl, astats_all_dev);
+  V4L_LAUNCH_CHECK();
+  PhaseScope ps("vf.bwd");
+  return v4l_net_backward(vf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, tr->g_vf, stream);
+}
+// a2c.py:61-74, 79-80 (pf.update(obs, acts), policy_loss, policy_loss.backward())
+static int a2c_actor_stage(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev, void* stream) {
+  int rc;
+  hipStream_t s = (hipStream_t)stream;
+  v4l_net* pf = tr->pf;
+  const int* rowidx = tr->rowidx_cur;
+  const Layout Lp = pf->layout(n);
+  if ((rc = v4l_net_pack(pf, stream))) return rc;  // the previous update's policy step moved the weights
+  { PhaseScope ps("pf.fwd");
+  if ((rc = v4l_net_forward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, 1, stream))) return rc; }
+  g_op = "loss";
+  {
+    ActorArgs aa;
+    memset(&aa, 0, sizeof(aa));
+    aa.mean = tr->ws + Lp.out; aa.logstd = pf->p[pf->logstd];
+    aa.acts = ro->acts_dev; aa.adv = ro->advs_dev; aa.rowidx = rowidx;
+    aa.n = n; aa.A = pf->cfg.out_dim; aa.inv_n = 1.f / (float)n; aa.ent_coef = hp->entropy_coeff;
+    aa.dmean = tr->ws + Lp.dout; aa.dlogstd = tr->g_pf + pf->params[pf->logstd].goff; aa.st = tr->stats_cur;
+    aa.tanh_action = pf->cfg.tanh_action;
+    aa.gscale = v4l_net_grad_scale(pf, n);
+    const dim3 blk(n >= 512 ? 1024 : 256);
+    rc = act_cap(aa.A) != ACT_CAP_NARROW ? launch_a2c_loss<V4L_MAX_ACT>(s, aa, tr->ctl, astats_all_dev, blk)
+                                         : launch_a2c_loss<ACT_CAP_NARROW>(s, aa, tr->ctl, astats_all_dev, blk);
+    if (rc) return rc;
+  }
+  PhaseScope ps("pf.bwd");
+  return v4l_net_backward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, tr->g_pf, stream);
+}
+int v4l_trainer_a2c_critic_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,
+                                 void* stream) {
+  int rc = check_a2c_args(tr, ro, n, hp, astats_all_dev);
+  if (rc) return rc;
+  V4L_REQUIRE(!capturing((hipStream_t)stream), "v4l_trainer_a2c_critic_grads: called under a caller's stream capture");
+  return a2c_critic_stage(tr, ro, n, hp, astats_all_dev, stream);
+}
+int v4l_trainer_a2c_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,
+                                void* stream) {
+  int rc = check_a2c_args(tr, ro, n, hp, astats_all_dev);
+  if (rc) return rc;
+  V4L_REQUIRE(!capturing((hipStream_t)stream), "v4l_trainer_a2c_actor_grads: called under a caller's stream capture");
+  return a2c_actor_stage(tr, ro, n, hp, astats_all_dev, stream);
+}
+static int run_a2c_update(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev, void* stream) {
+  int rc;  // (critic first, as the PPO update: with disjoint parameter sets the two steps of a2c.py:79-87 are independent)
+  if ((rc = a2c_critic_stage(tr, ro, n, hp, astats_all_dev, stream))) return rc;
+  if ((rc = v4l_trainer_critic_step(tr, hp, stream))) return rc;
+  if ((rc = a2c_actor_stage(tr, ro, n, hp, astats_all_dev, stream))) return rc;
+  return v4l_trainer_actor_step(tr, hp, stream);
+}
+static void a2c_graph_key(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, const float* astats_all_dev,
+                          A2cGraphKey* key) {
+  memset(key, 0, sizeof(*key));
+  key->base.ro = *ro; memcpy(&key->base.hp, hp, sizeof(*hp)); key->base.n = n;  // (bytewise: v4l_ppo_hyper ends in padding)
+  key->base.gen[0] = tr->pf->gen; key->base.gen[1] = tr->vf->gen; key->base.gen[2] = tr->tpf->gen;
+  key->astats_all = astats_all_dev;
+}
+// Captures `count` A2C updates on s into *exec
+static int capture_a2c(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev, int count,
+                       hipStream_t s, hipGraphExec_t* exec) {
+  hipGraph_t graph = nullptr;
+  int rc = 0;
+  V4L_TRACE("a2c update: begin capture of %d update(s)", count);
+  V4L_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  for (int u = 0; u < count && !rc; ++u) rc = run_a2c_update(tr, ro, n, hp, astats_all_dev, (void*)s);
+  const hipError_t e = hipStreamEndCapture(s, &graph);
+  if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+  V4L_HIP_CHECK(e);
+  V4L_HIP_CHECK(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
+  V4L_HIP_CHECK(hipGraphDestroy(graph));
+  ++tr->a2c_captures;
+  V4L_TRACE("a2c update: instantiated");
+  return 0;
+}
+int v4l_trainer_a2c_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,
+                                int use_graph, void* stream) {
+  int rc = check_a2c_args(tr, ro, n, hp, astats_all_dev);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  V4L_REQUIRE(!capturing(s), "v4l_trainer_a2c_update_next: called under a caller's stream capture (use_graph = 1 captures itself)");
+  drop_ppo_graph(tr);
+  drop_vmpo_graph(tr);
+  if (!use_graph || g_prof || s == nullptr) return run_a2c_update(tr, ro, n, hp, astats_all_dev, stream);
+  A2cGraphKey key;
+  a2c_graph_key(tr, ro, n, hp, astats_all_dev, &key);
+  if (memcmp(&key, &tr->akey, sizeof(key)) != 0) { drop_a2c_graph(tr); tr->akey = key; }
+  if (!tr->awarm) {  // first update of a configuration runs eagerly: it uploads the descriptor tables
+    tr->awarm = true;
+    return run_a2c_update(tr, ro, n, hp, astats_all_dev, stream);
+  }
+  if (tr->aexec == nullptr && (rc = capture_a2c(tr, ro, n, hp, astats_all_dev, 1, s, &tr->aexec))) return rc;
+  V4L_HIP_CHECK(hipGraphLaunch(tr->aexec, s));
+  ++tr->a2c_replays;
+  return 0;
+}
+int v4l_trainer_a2c_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,
+                               int count, int use_graph, void* stream) {
+  int rc = check_a2c_args(tr, ro, n, hp, astats_all_dev);
+  if (rc) return rc;
+  V4L_REQUIRE(count >= 1, "v4l_trainer_a2c_update_run: count must be >= 1");
+  hipStream_t s = (hipStream_t)stream;
+  V4L_REQUIRE(!capturing(s), "v4l_trainer_a2c_update_run: called under a caller's stream capture (use_graph = 1 captures itself)");
+  A2cGraphKey key;
+  a2c_graph_key(tr, ro, n, hp, astats_all_dev, &key);
+  const bool same = memcmp(&key, &tr->akey, sizeof(key)) == 0;
+  if (!use_graph || g_prof || s == nullptr || !same || !tr->awarm) {
+    // no graph, or a configuration this trainer has not run yet: update by update (the first one eagerly, then single-update
+    // replays); the next call captures the whole run
+    for (int u = 0; u < count; ++u)
+      if ((rc = v4l_trainer_a2c_update_next(tr, ro, n, hp, astats_all_dev, use_graph, stream))) return rc;
+    return 0;
+  }
+  if (tr->aexec_run != nullptr && tr->aexec_run_count != count) {
+    (void)hipGraphExecDestroy(tr->aexec_run);
+    tr->aexec_run = nullptr;
+  }
+  if (tr->aexec_run == nullptr) {
+    if ((rc = capture_a2c(tr, ro, n, hp, astats_all_dev, count, s, &tr->aexec_run))) return rc;
+    tr->aexec_run_count = count;
+  }
+  V4L_HIP_CHECK(hipGraphLaunch(tr->aexec_run, s));
+  ++tr->a2c_replays;
+  return 0;
+}
+int v4l_trainer_a2c_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays) {
+  V4L_REQUIRE(tr && captures && replays, "v4l_trainer_a2c_graph_counts: null argument");
+  *captures = tr->a2c_captures;
+  *replays = tr->a2c_replays;
   return 0;
 }
 

@@ -655,6 +655,44 @@ class HipTrainer:
     check(self.L.v4l_trainer_vmpo_graph_counts(self.h, C.byref(cap), C.byref(rep)), "v4l_trainer_vmpo_graph_counts")
     return cap.value, rep.value
 
+  # ---- A2C (torchrl/algo/on_policy/a2c.py:46-107) on state-MLP nets: two loss launches of its own between the phases above.
+  # astats_all: [U][V4L_A2C_STATS] float32 device tensor of the open run's A2C records (zeroed by the caller)
+  def a2c_critic_grads(self, ro, n, astats_all):
+    """a2c.py:76-77, 84-85 up to vf_loss.backward() (v4l_trainer_a2c_critic_grads); critic_step() follows."""
+    self._pre(n)
+    check(self.L.v4l_trainer_a2c_critic_grads(self.h, C.byref(ro), n, C.byref(self.hp), _ptr(astats_all), _stream()),
+          "v4l_trainer_a2c_critic_grads")
+
+  def a2c_actor_grads(self, ro, n, astats_all):
+    """a2c.py:61-74, 79-80 up to policy_loss.backward() (v4l_trainer_a2c_actor_grads); actor_step() follows."""
+    check(self.L.v4l_trainer_a2c_actor_grads(self.h, C.byref(ro), n, C.byref(self.hp), _ptr(astats_all), _stream()),
+          "v4l_trainer_a2c_actor_grads")
+
+  def a2c_update_next(self, ro, n, astats_all, graph=False):
+    """The next A2C minibatch update of the run begin() opened (v4l_trainer_a2c_update_next). graph=True: one hipGraph replay
+    once the configuration has run; graph=False: eager launches."""
+    self._pre(n)
+    check(self.L.v4l_trainer_a2c_update_next(self.h, C.byref(ro), n, C.byref(self.hp), _ptr(astats_all), int(graph), _stream()),
+          "v4l_trainer_a2c_update_next")
+    self._count(1)
+    self._after_steps()
+
+  def a2c_update_run(self, ro, n, count, astats_all, graph=True):
+    """The next `count` A2C updates behind one begin(): with graph=True ONE hipGraph replay for all of them
+    (v4l_trainer_a2c_update_run). Keep the row-index, record and astats_all tensors at one address from run to run: the graph is
+    keyed on them."""
+    self._pre(n)
+    check(self.L.v4l_trainer_a2c_update_run(self.h, C.byref(ro), n, C.byref(self.hp), _ptr(astats_all), int(count), int(graph),
+                                            _stream()), "v4l_trainer_a2c_update_run")
+    self._count(int(count))
+    self._after_steps()
+
+  def a2c_graph_counts(self):
+    """-> (A2C graphs instantiated, A2C graph replays launched) since this trainer was created."""
+    cap, rep = C.c_int64(0), C.c_int64(0)
+    check(self.L.v4l_trainer_a2c_graph_counts(self.h, C.byref(cap), C.byref(rep)), "v4l_trainer_a2c_graph_counts")
+    return cap.value, rep.value
+
 
 def vmpo_select(adv, rowidx, n):
   """v4l_vmpo_select: the slots of the ceil(n / 2) rows with the largest adv[slot] in descending order (ties to the earlier

@@ -9,6 +9,7 @@ stays the reference's, so `starter/ppo_*.py` runs unchanged:
     overlay.install()                 # pf.explore / vf / PPO.update / GAE on the HIP engine, reference collector
     overlay.install(fast_path=True)   # + fused rollout step, HBM-resident replay buffer, pinned observation upload
     overlay.install(vmpo=True)        # + `torchrl.algo.VMPO` on the HIP engine (opt-in: the default leaves it the reference's)
+    overlay.install(a2c=True)         # + `torchrl.algo.A2C` on the HIP engine, state-MLP nets only (opt-in, like vmpo)
 
 Rebinding is by name on every already-imported `torchrl.<pkg>` module that defines the name (the package and the
 sub-module that holds the class: `from torchrl.algo import PPO`, `from torchrl.algo.on_policy.ppo import PPO` and
@@ -43,6 +44,11 @@ VMPO_NAMES = {
     "algo": ["VMPO"],
 }
 
+# a2c=True: the plain actor-critic both learners derive from (`from torchrl.algo import A2C`)
+A2C_NAMES = {
+    "algo": ["A2C"],
+}
+
 _installed = {}
 
 
@@ -60,9 +66,10 @@ def _rebind(ref_pkg_name, name, obj, always_on_package=False):
     return hits
 
 
-def install(fast_path=False, reference_package="torchrl", vmpo=False):
+def install(fast_path=False, reference_package="torchrl", vmpo=False, a2c=False):
     """Rebind the hot-path classes on the reference's `torchrl`. Returns {"pkg.name": [modules patched]}.
-    vmpo=True also rebinds `torchrl.algo.VMPO` (vision4leg_amd.torchrl.algo.VMPO); without it VMPO stays the reference's."""
+    vmpo=True also rebinds `torchrl.algo.VMPO` (vision4leg_amd.torchrl.algo.VMPO); without it VMPO stays the reference's.
+    a2c=True also rebinds `torchrl.algo.A2C` (and nothing else); without it A2C stays the reference's."""
     ref = importlib.import_module(reference_package)
     if getattr(ref, "__v4l_shell__", False):
         raise RuntimeError("vision4leg_amd.overlay: `%s` resolves to the HIP shell itself; put the reference "
@@ -88,8 +95,10 @@ def install(fast_path=False, reference_package="torchrl", vmpo=False):
             shell = importlib.import_module("vision4leg_amd.torchrl." + pkg)
             for name, shell_name in names.items():
                 report["%s.%s" % (pkg, name)] = _rebind(ref_name, name, getattr(shell, shell_name))
-    if vmpo:
-        for pkg, names in VMPO_NAMES.items():
+    for wanted, table in ((vmpo, VMPO_NAMES), (a2c, A2C_NAMES)):
+        if not wanted:
+            continue
+        for pkg, names in table.items():
             ref_name = "%s.%s" % (reference_package, pkg)
             shell = importlib.import_module("vision4leg_amd.torchrl." + pkg)
             for name in names:

@@ -31,7 +31,10 @@ class RolloutActor:
 
     def __init__(self, pf, vf, env_nums, graph=False):
         from ...engine import HipActor
-        self._actor = HipActor(pf.hip, vf.hip, env_nums, graph=graph)
+        # every starter hands one encoder / base module to both nets; a pair without a common parameter (what algo.A2C takes)
+        # runs each net's own encoder: the layer-by-layer step
+        shared = bool({id(p) for p in pf.parameters()} & {id(p) for p in vf.parameters()})
+        self._actor = HipActor(pf.hip, vf.hip, env_nums, shared_encoder=shared, graph=graph)
 
     def attach(self, rollout):
         self._actor.attach(rollout)
