@@ -89,6 +89,11 @@ extern "C" {
 #define V4L_ACT_RELU 0
 #define V4L_ACT_TANH 1
 
+/* where a net's log sigma comes from (v4l_net_cfg.has_logstd) */
+#define V4L_LOGSTD_NONE 0
+#define V4L_LOGSTD_PARAM 1
+#define V4L_LOGSTD_HEAD 2
+
 #define V4L_MAX_HIDDEN 4
 #define V4L_STATS 24 /* floats per update record; [0..17] = the 18 logger keys of ppo.py:77-92,122-123,142-145;
                         [18..21] shard moments of the advantages (data-parallel exchange); [22] = how many of the 18 are
@@ -117,7 +122,13 @@ typedef struct v4l_net_cfg {
   int ff_dim;          /* V4L_NET_LOCO: dim_feedforward                                                  */
   int n_head_hidden;   /* append_hidden_shapes (nets.py:35-50, 224-243, 973-992)                         */
   int head_hidden[V4L_MAX_HIDDEN];
-  int has_logstd;      /* 1: Gaussian policy with a state-independent logstd parameter                   */
+  int has_logstd;      /* V4L_LOGSTD_*: 0 not a policy (value net); 1 Gaussian policy with a state-independent logstd
+                          parameter; 2 (version 113) GaussianContPolicy (policies/continuous_policy.py:222-236), the Gaussian
+                          policy whose log sigma is state dependent: out_dim = 2 A is the width of the head's last layer,
+                          `x.chunk(2, -1)` makes columns 0 .. A-1 of the [n][V4L_OUT_LD] output row the mean and columns
+                          A .. 2A-1 the raw log sigma (clamped to [-5, 2] and exponentiated per row); the same columns of the
+                          d(out) row carry d(loss)/d(raw log sigma). No `logstd` parameter. V4L_NET_MLP only, out_dim even and
+                          <= V4L_OUT_LD (A = 1 .. 8). The struct keeps its size and every field its offset                 */
   int tanh_action;     /* Gaussian policy with tanh_action=True (policies/distribution.py:5-80 TanhNormal,
                           continuous_policy.py:85-146): action = tanh(mean + std * eps), log-prob of a stored action through
                           atanh(action) with the -log(1 - a^2 + 1e-6) correction. The fused rollout step kernels sample through
@@ -209,6 +220,11 @@ int v4l_gauss_head(const float* meanp_dev, const float* logstd_dev, const float*
 int v4l_gauss_head_tanh(const float* out_dev, const float* logstd_dev, const float* acts_dev, const float* pre_tanh_dev, int n,
                         int A, float* mean_dev, float* std_dev, float* logstd_clamped_dev, float* ent_dev, float* logp_dev,
                         void* stream);
+/* the same for a V4L_LOGSTD_HEAD policy (GaussianContPolicy.forward, continuous_policy.py:222-236; version 113): out_dev is the
+ * [n][V4L_OUT_LD] head output whose columns A .. 2A-1 are the raw log sigma. mean / std / clamped log_std are [n][A], ent and
+ * log_prob [n]. tanh_action / pre_tanh_dev as in v4l_gauss_head_tanh. 1 <= A <= V4L_OUT_LD / 2. */
+int v4l_gauss_head_sd(const float* out_dev, const float* acts_dev, const float* pre_tanh_dev, int n, int A, int tanh_action,
+                      float* mean_dev, float* std_dev, float* logstd_clamped_dev, float* ent_dev, float* logp_dev, void* stream);
 /* column 0 of a padded head output -> contiguous [n] (vf(x) for the collector, collector/on_policy.py:99-100) */
 int v4l_col0(const float* src_dev, int n, float* dst_dev, void* stream);
 
@@ -524,6 +540,10 @@ int64_t v4l_prof_collect(char* buf, int64_t cap);
 /* (diagnostic builds compiled with -DV4L_INFER_TIMING additionally export a clock64 phase-stamp reader used by
  * tools/probe/stamps*.py; it is not part of this ABI and absent from the shipped library.) */
 
+/* ---- introspection for tests (version 113): the name of the kernel family a step of this actor runs on — "MLP_ONE_BLOCK",
+ * "MLP_PER_SAMPLE", "CNN_DENSE", "CNN_PER_SAMPLE", "STACK_TOK16", "STACK_TOK17", "STACK_F32ENC" or "GENERAL" (the two state-MLP
+ * kernels log the same profiler label). A static string. */
+const char* v4l_actor_route(const v4l_actor* actor, int shared_encoder);
 /* ---- introspection for tests: float offset of a named activation inside a workspace laid out for n rows
  * ("c1","c2","c3","eh<i>","x<l>","qkv<l>","P<l>","ctx<l>","mid<l>","ff<l>","xin<l>","xh1_<l>","rs1_<l>","pooled","hh<i>",
  * "out","dout", and after a backward pass "dz2_<l>","df<l>","dz1_<l>","dqkv<l>","dx<l>","dhh<i>","deh<i>","dpool","dc1".."dc3");

@@ -13,6 +13,7 @@ SRC_DIR = os.path.join(_HERE, "csrc")
 V4L_F32, V4L_BF16, V4L_F16 = 0, 1, 2
 V4L_NET_MLP, V4L_NET_CNN, V4L_NET_LOCO, V4L_NET_CNN_VIS, V4L_NET_LOCO_VIS = 0, 1, 2, 3, 4
 V4L_ACT_RELU, V4L_ACT_TANH = 0, 1
+V4L_LOGSTD_NONE, V4L_LOGSTD_PARAM, V4L_LOGSTD_HEAD = 0, 1, 2  # NetCfg.has_logstd: value net / logstd parameter / log sigma from the head
 V4L_MAX_HIDDEN = 4
 V4L_STATS = 24
 ST_NONFINITE = 22   # record slot: number of NaN / Inf among the 18 logged scalars of an update
@@ -120,6 +121,7 @@ _SIGS = {
   "v4l_net_backward": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P]),
   "v4l_gauss_head": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
   "v4l_gauss_head_tanh": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+  "v4l_gauss_head_sd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
   "v4l_col0": (C.c_int, [_P, C.c_int, _P, _P]),
   "v4l_gae": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                         _P, _P, _P, _P, _P, _P]),
@@ -135,6 +137,7 @@ _SIGS = {
   "v4l_actor_check": (C.c_int, [_P, C.POINTER(C.c_int), _P]),
   "v4l_actor_step": (C.c_int, [_P] + [_P] * 12 + [C.c_int, C.c_int, _P]),
   "v4l_actor_split_supported": (C.c_int, [_P, C.c_int]),
+  "v4l_actor_route": (C.c_char_p, [_P, C.c_int]),
   "v4l_actor_step_split": (C.c_int, [_P] + [_P] * 13 + [C.c_int, _P]),
   "v4l_trainer_create": (C.c_int, [_P, _P, _P, C.POINTER(_P)]),
   "v4l_trainer_destroy": (None, [_P]),

@@ -319,18 +319,20 @@ __device__ __forceinline__ float tanh_corr(float a) { return logf(1.f - a * a + 
 // GaussianContPolicyBase.explore (continuous_policy.py:85-125) + the value read-out of the collector
 // (collector/on_policy.py:95-100) for one env step: action = mean + std * eps (== Normal(mean,std).sample() given the
 // same standard-normal draws), entropy, value; also files action and value into the rollout arrays and advances t.
-__global__ __launch_bounds__(256) void act_finish_kernel(ActCtl* c, const float* __restrict__ meanp,
-                                                         const float* __restrict__ logstd, const float* __restrict__ valuep,
-                                                         const float* __restrict__ eps, int E, int A,
-                                                         float* __restrict__ acts_roll, float* __restrict__ values_roll,
-                                                         float* __restrict__ logp_roll, float* __restrict__ action,
-                                                         float* __restrict__ mean, float* __restrict__ stdv,
-                                                         float* __restrict__ ent, float* __restrict__ value, int tanh_action) {
+// SD (GaussianContPolicy, continuous_policy.py:222-236): log sigma is columns A .. 2A-1 of the row's own head output, `logstd` unused
+template <bool SD>
+__device__ __forceinline__ void act_finish_body(ActCtl* c, const float* __restrict__ meanp,
+                                                const float* __restrict__ logstd, const float* __restrict__ valuep,
+                                                const float* __restrict__ eps, int E, int A,
+                                                float* __restrict__ acts_roll, float* __restrict__ values_roll,
+                                                float* __restrict__ logp_roll, float* __restrict__ action,
+                                                float* __restrict__ mean, float* __restrict__ stdv,
+                                                float* __restrict__ ent, float* __restrict__ value, int tanh_action) {
   const long long t = c->t;
   for (int i = threadIdx.x; i < E; i += 256) {
     float e = 0.f, lp = 0.f;
     for (int a = 0; a < A; ++a) {
-      const float ls = fminf(fmaxf(logstd[a], LOG_SIG_MIN), LOG_SIG_MAX);
+      const float ls = fminf(fmaxf(SD ? meanp[(int64_t)i * OUT_LD + A + a] : logstd[a], LOG_SIG_MIN), LOG_SIG_MAX);
       const float sg = expf(ls);
       e += 0.5f + HALF_LOG_2PI + logf(sg);
       const float mu = meanp[(int64_t)i * OUT_LD + a];
@@ -355,6 +357,27 @@ __global__ __launch_bounds__(256) void act_finish_kernel(ActCtl* c, const float*
   }
   __syncthreads();
   if (threadIdx.x == 0) c->t = t + 1;
+}
+__global__ __launch_bounds__(256) void act_finish_kernel(ActCtl* c, const float* __restrict__ meanp,
+                                                         const float* __restrict__ logstd, const float* __restrict__ valuep,
+                                                         const float* __restrict__ eps, int E, int A,
+                                                         float* __restrict__ acts_roll, float* __restrict__ values_roll,
+                                                         float* __restrict__ logp_roll, float* __restrict__ action,
+                                                         float* __restrict__ mean, float* __restrict__ stdv,
+                                                         float* __restrict__ ent, float* __restrict__ value, int tanh_action) {
+  act_finish_body<false>(c, meanp, logstd, valuep, eps, E, A, acts_roll, values_roll, logp_roll, action, mean, stdv, ent, value,
+                         tanh_action);
+}
+// the same for a policy whose head row carries its own log sigma (v4l_net_cfg.has_logstd == V4L_LOGSTD_HEAD): sigma, entropy
+// and log-prob per row
+__global__ __launch_bounds__(256) void act_finish_sd_kernel(ActCtl* c, const float* __restrict__ outp,
+                                                            const float* __restrict__ valuep, const float* __restrict__ eps, int E,
+                                                            int A, float* __restrict__ acts_roll, float* __restrict__ values_roll,
+                                                            float* __restrict__ logp_roll, float* __restrict__ action,
+                                                            float* __restrict__ mean, float* __restrict__ stdv,
+                                                            float* __restrict__ ent, float* __restrict__ value, int tanh_action) {
+  act_finish_body<true>(c, outp, nullptr, valuep, eps, E, A, acts_roll, values_roll, logp_roll, action, mean, stdv, ent, value,
+                        tanh_action);
 }
 
 // --------------------------------------------------------------------------------- block reductions
@@ -765,6 +788,107 @@ __device__ __forceinline__ void actor_loss_body(const ActorArgs& p) {
 }
 template <bool TANH, int CAP>
 __global__ __launch_bounds__(1024) void actor_loss_kernel(ActorArgs p) { actor_loss_body<TANH, CAP>(p); }
+
+// The sibling for GaussianContPolicy (continuous_policy.py:222-236; v4l_net_cfg.has_logstd == V4L_LOGSTD_HEAD): log sigma is
+// state dependent — columns A .. 2A-1 of the row's own [OUT_LD] head output (p.mean; the frozen target's in p.tmean), clamped and exponentiated per
+// row — so nothing is hoisted out of the row loop, the gradient w.r.t. the raw log sigma leaves in columns A .. 2A-1 of the d(out)
+// row (through grad_out like d(mean): those columns pass the backward's contractions) and log_std/* are the statistics of the
+// clamped [n][A] tensor (ppo.py:84-87). p.logstd, p.tlogstd and p.dlogstd are unused. A <= ACT_CAP_NARROW. Single block.
+// The mean half comes in with 16-byte loads; the log-sigma half starts at column A, unaligned for odd A and at a run-time offset:
+// read as A scalar loads of the cache line the row loads just fetched, never as a run-time index into a register array.
+template <bool TANH>
+__device__ __forceinline__ void actor_loss_sd_body(const ActorArgs& p) {
+  constexpr int CAP = ACT_CAP_NARROW;
+  const int n = p.n, A = p.A;
+  const bool stored = p.logp_old != nullptr;
+  const float amean = p.st[ST_ADV_MEAN], astd = p.st[ST_ADV_STD];
+  const float dent = p.ent_coef * p.inv_n;  // d(-ent_coef * mean_i(ent_i))/d(log sigma_ia), sign below
+  double s_lp = 0.0, s_lp2 = 0.0, s_sur = 0.0, s_ent = 0.0, s_ls = 0.0, s_ls2 = 0.0;
+  int sat = 0;
+  float lp_mx = -INFINITY, lp_mn = INFINITY, r_mx = -INFINITY, r_mn = INFINITY, ls_mx = -INFINITY, ls_mn = INFINITY;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int slot = p.rowidx ? p.rowidx[i] : i;
+    const float* __restrict__ row = p.mean + (int64_t)i * OUT_LD;
+    const float* __restrict__ trow = stored ? row : p.tmean + (int64_t)i * OUT_LD;
+    float mu[CAP], tmu[CAP], dm[CAP], dl[CAP];
+    actor_load_row(row, mu);
+    if (!stored) actor_load_row(trow, tmu);
+    float lp = 0.f, lpo = 0.f, ent = 0.f;
+    unsigned open = 0;  // bit a: raw log sigma_a inside [LOG_SIG_MIN, LOG_SIG_MAX] — the clamp passes its gradient
+    // pass 1 over the dimensions: log pi, log pi_old, entropy, log_std statistics; keeps d / var and z^2 - 1 for pass 2
+#pragma unroll
+    for (int a = 0; a < CAP; ++a) {
+      dm[a] = 0.f; dl[a] = 0.f;
+      if (a < A) {
+        const float raw = row[A + a];
+        const float ls = fminf(fmaxf(raw, LOG_SIG_MIN), LOG_SIG_MAX);
+        const float sg = expf(ls), lsg = logf(sg);
+        const float act = p.acts[(int64_t)slot * A + a];
+        const float x = TANH ? tanh_pre(act) : act;
+        const float corr = TANH ? tanh_corr(act) : 0.f;
+        const float d = x - mu[a];
+        const float var = sg * sg;
+        lp += -(d * d) / (2.f * var) - lsg - HALF_LOG_2PI - corr;
+        dm[a] = d / var;
+        dl[a] = d * d / var - 1.f;
+        open |= (raw >= LOG_SIG_MIN && raw <= LOG_SIG_MAX) ? 1u << a : 0u;  // torch.clamp passes the gradient at both ends
+        ent += 0.5f + HALF_LOG_2PI + lsg;
+        s_ls += ls; s_ls2 += (double)ls * ls;
+        ls_mx = fmaxf(ls_mx, ls); ls_mn = fminf(ls_mn, ls);
+        if (!stored) {
+          const float tls = fminf(fmaxf(trow[A + a], LOG_SIG_MIN), LOG_SIG_MAX);
+          const float tsg = expf(tls), tlsg = logf(tsg);
+          const float dt = x - tmu[a];
+          lpo += -(dt * dt) / (2.f * tsg * tsg) - tlsg - HALF_LOG_2PI - corr;
+        }
+      }
+    }
+    if (stored) lpo = p.logp_old[slot];  // stored when the action was taken (== the target policy's)
+    const float ratio = expf(lp - lpo);
+    const float an = (p.adv[slot] - amean) / (astd + 1e-5f);
+    const float pre = ratio * an;
+    const float clp = fminf(fmaxf(ratio, 1.f - p.clip), 1.f + p.clip) * an;
+    const float dlp = !(pre > clp) ? -p.inv_n * an * ratio : 0.f;  // (see actor_row)
+    s_sur += fminf(pre, clp);
+    s_ent += ent;
+    s_lp += lp; s_lp2 += (double)lp * lp;
+    lp_mx = fmaxf(lp_mx, lp); lp_mn = fminf(lp_mn, lp);
+    r_mx = fmaxf(r_mx, ratio); r_mn = fminf(r_mn, ratio);
+    // pass 2: the d(out) row — [d mean | d raw log sigma | zeros], every one of the OUT_LD columns written exactly once
+    float* __restrict__ drow = p.dmean + (int64_t)i * OUT_LD;
+#pragma unroll
+    for (int a = 0; a < CAP; ++a) {
+      if (a < A) {
+        drow[a] = grad_out(dlp * dm[a], p.gscale, sat);
+        // outside the clamp's range: exactly 0, whatever the slope (and not counted as a clamped element)
+        drow[A + a] = (open >> a & 1u) ? grad_out(dlp * dl[a] - dent, p.gscale, sat) : 0.f;
+      }
+    }
+    for (int c = 2 * A; c < OUT_LD; ++c) drow[c] = 0.f;
+  }
+  Red4 r1 = block_red4(s_lp, s_lp2, lp_mx, lp_mn);
+  Red4 r2 = block_red4(s_sur, (double)sat, r_mx, r_mn);
+  Red4 r3 = block_red4(s_ls, s_ls2, ls_mx, ls_mn);
+  Red4 r4 = block_red4(s_ent, 0.0, 0.f, 0.f);
+  if (threadIdx.x == 0) {
+    float* st = p.st;
+    const double lpm = r1.s / n;
+    // -mean(sur) - ent_coef * mean_i(sum_a(0.5 + log(2 pi) / 2 + log sigma_ia))
+    st[ST_PI_LOSS] = (float)(-(r2.s / n) - (double)p.ent_coef * (r4.s / n));
+    st[ST_LP_MEAN] = (float)lpm;
+    st[ST_LP_STD] = (float)sqrt(fmax(0.0, (r1.s2 - n * lpm * lpm) / (double)(n - 1)));
+    st[ST_LP_MAX] = r1.mx; st[ST_LP_MIN] = r1.mn;
+    st[ST_RATIO_MAX] = r2.mx; st[ST_RATIO_MIN] = r2.mn;
+    if (p.gscale != 1.f) st[ST_F16_SAT] += (float)r2.s2;
+    // log_std.mean() / .std() (Bessel, over all n * A elements) / .max() / .min() of the clamped tensor: finite at A = 1 for n >= 2
+    const double cnt = (double)n * A, lsm = r3.s / cnt;
+    st[ST_LS_MEAN] = (float)lsm;
+    st[ST_LS_STD] = cnt > 1.0 ? (float)sqrt(fmax(0.0, (r3.s2 - cnt * lsm * lsm) / (cnt - 1.0))) : NAN;
+    st[ST_LS_MAX] = r3.mx; st[ST_LS_MIN] = r3.mn;
+  }
+}
+template <bool TANH>
+__global__ __launch_bounds__(1024) void actor_loss_sd_kernel(ActorArgs p) { actor_loss_sd_body<TANH>(p); }
 #pragma clang fp contract(fast)
 
 // Gaussian head post-processing for the policy API (continuous_policy.py:85-146,486-492): from the padded
@@ -800,6 +924,36 @@ __global__ __launch_bounds__(256) void gauss_head_kernel(const float* __restrict
     ent[i] = e;
     if (acts != nullptr) logp[i] = lp;
   }
+}
+
+// The same for GaussianContPolicy.forward (continuous_policy.py:222-236): `mean, log_std = x.chunk(2, -1)` of the padded head
+// output outp [n][OUT_LD], log_std clamped and exponentiated per row: mean / std / clamped log_std [n][A], ent [n], log_prob [n].
+__global__ __launch_bounds__(256) void gauss_head_sd_kernel(const float* __restrict__ outp, const float* __restrict__ acts, int n,
+                                                            int A, float* __restrict__ mean, float* __restrict__ stdv,
+                                                            float* __restrict__ logstd_c, float* __restrict__ ent,
+                                                            float* __restrict__ logp, int tanh_action,
+                                                            const float* __restrict__ pre_tanh) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float e = 0.f, lp = 0.f;
+  for (int a = 0; a < A; ++a) {
+    const float mu = outp[(int64_t)i * OUT_LD + a];
+    const float ls = fminf(fmaxf(outp[(int64_t)i * OUT_LD + A + a], LOG_SIG_MIN), LOG_SIG_MAX);
+    const float sg = expf(ls), lsg = logf(sg);
+    e += 0.5f + HALF_LOG_2PI + lsg;
+    mean[(int64_t)i * A + a] = mu;
+    stdv[(int64_t)i * A + a] = sg;
+    logstd_c[(int64_t)i * A + a] = ls;
+    if (acts != nullptr) {
+      const float act = acts[(int64_t)i * A + a];
+      const float x = !tanh_action ? act : (pre_tanh != nullptr ? pre_tanh[(int64_t)i * A + a] : tanh_pre(act));
+      const float d = x - mu;
+      lp += -(d * d) / (2.f * sg * sg) - lsg - HALF_LOG_2PI;
+      if (tanh_action) lp -= tanh_corr(act);
+    }
+  }
+  ent[i] = e;
+  if (acts != nullptr) logp[i] = lp;
 }
 
 // Copy column 0 of a padded head output to a contiguous [n] vector (critic values for the collector).

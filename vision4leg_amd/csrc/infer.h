@@ -2413,7 +2413,9 @@ template <int ACT> __device__ __forceinline__ float hidden_act(float x) {
   else return fmaxf(x, 0.f);
 }
 struct InfMlp { const void *wf1, *wf2; const float *bf1, *bf2; int S, Sp, Kp1; };
-template <typename T, int ACT = V4L_ACT_RELU>
+// SD (GaussianContPolicy, continuous_policy.py:222-236; v4l_net_cfg.has_logstd == V4L_LOGSTD_HEAD): the policy's head row is [mean | raw log sigma],
+// the epilogue reads sigma from the row it just computed (so[A + a]) — a compile-time choice, like ACT
+template <typename T, int ACT = V4L_ACT_RELU, bool SD = false>
 __global__ __launch_bounds__(1024) void rollout_mlp_kernel(const ActCtl* __restrict__ ctlc, const float* __restrict__ obs, int E,
                                                            InfMlp w, InfCnnHeadPair hd, InfFinish fin,
                                                            float* __restrict__ state_roll) {
@@ -2467,7 +2469,7 @@ __global__ __launch_bounds__(1024) void rollout_mlp_kernel(const ActCtl* __restr
       float e = 0.f, lp = 0.f;
       for (int a = 0; a < A; ++a) {
         const float mu = so[a];
-        const float ls = fminf(fmaxf(fin.logstd[a], LOG_SIG_MIN), LOG_SIG_MAX);
+        const float ls = fminf(fmaxf(SD ? so[A + a] : fin.logstd[a], LOG_SIG_MIN), LOG_SIG_MAX);
         const float sg = expf(ls);
         e += 0.5f + HALF_LOG_2PI + logf(sg);
         float act = fmaf(sg, fin.eps[(int64_t)i * A + a], mu);

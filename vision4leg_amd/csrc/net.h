@@ -126,6 +126,10 @@ struct v4l_net {
   const float* acts16_c1 = nullptr;  // the c1 slot (= the workspace) whose c1 / c2 currently hold the operand type; null: none
   bool vis_only() const { return cfg.kind == V4L_NET_CNN_VIS || cfg.kind == V4L_NET_LOCO_VIS; }
   bool is_tf() const { return cfg.kind == V4L_NET_LOCO || cfg.kind == V4L_NET_LOCO_VIS; }
+  // GaussianContPolicy (continuous_policy.py:222-236): the head's last layer is [mean | raw log sigma], out_dim = 2 A columns
+  bool sd() const { return cfg.has_logstd == V4L_LOGSTD_HEAD; }
+  // action dimensions A of a policy: the head's width, or half of it where the other half is the per-row log sigma
+  int act_dim() const { return sd() ? cfg.out_dim / 2 : cfg.out_dim; }
   std::vector<v4l::ParamInfo> params;
   int64_t total_params = 0;
   // layers

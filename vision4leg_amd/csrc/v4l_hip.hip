@@ -860,6 +860,16 @@ int v4l_net::build() {
               "V4L_NET_LOCO, V4L_NET_CNN_VIS and V4L_NET_LOCO_VIS take V4L_ACT_RELU", c.kind);
   V4L_REQUIRE(c.out_dim > 0 && c.out_dim <= V4L_MAX_ACT, "v4l_net_create: 1<=out_dim<=%d (V4L_MAX_ACT) required, got %d", V4L_MAX_ACT,
               c.out_dim);
+  V4L_REQUIRE(c.has_logstd >= V4L_LOGSTD_NONE && c.has_logstd <= V4L_LOGSTD_HEAD,
+              "v4l_net_create: has_logstd must be 0 (none), 1 (a logstd parameter) or 2 (log sigma from the head's last layer), got %d",
+              c.has_logstd);
+  if (sd()) {  // GaussianContPolicy (continuous_policy.py:222-236): the last layer is [mean | raw log sigma]
+    V4L_REQUIRE(c.kind == V4L_NET_MLP, "v4l_net_create: V4L_LOGSTD_HEAD runs on net kind V4L_NET_MLP only (got kind %d)", c.kind);
+    V4L_REQUIRE(c.out_dim % 2 == 0, "v4l_net_create: V4L_LOGSTD_HEAD splits the head's output in two halves: out_dim must be even, "
+                "got %d", c.out_dim);
+    V4L_REQUIRE(c.out_dim <= OUT_LD, "v4l_net_create: V4L_LOGSTD_HEAD needs 2 A <= %d columns of the head row, got out_dim %d", OUT_LD,
+                c.out_dim);
+  }
   if (vis_only())  // vision-only nets have no proprio branch: the observation row is the depth stack alone
     V4L_REQUIRE(c.state_dim == 0 && c.n_enc_hidden == 0, "v4l_net_create: vision-only nets take state_dim 0 and no encoder MLP");
   else
@@ -986,7 +996,7 @@ int v4l_net::build() {
       head[0].taps = 16;
     }
   }
-  if (c.has_logstd) logstd = add_param("logstd", {c.out_dim});
+  if (c.has_logstd == V4L_LOGSTD_PARAM) logstd = add_param("logstd", {c.out_dim});
 
   // ---- packed operand layout
   auto align64 = [](int64_t x) { return (x + 63) / 64 * 64; };
@@ -2239,7 +2249,8 @@ static InfFinish step_finish(const v4l_actor* a, const StepIO& io, hipStream_t s
   const v4l_net* pf = a->pf;
   InfFinish fin;
   memset(&fin, 0, sizeof(fin));
-  fin.ctl = a->ctl; fin.logstd = pf->p[pf->logstd]; fin.eps = io.eps; fin.A = pf->cfg.out_dim; fin.tanh_action = pf->cfg.tanh_action;
+  fin.ctl = a->ctl; fin.logstd = pf->logstd >= 0 ? pf->p[pf->logstd] : nullptr;  // (null: a V4L_LOGSTD_HEAD policy, sigma from the head row)
+  fin.eps = io.eps; fin.A = pf->act_dim(); fin.tanh_action = pf->cfg.tanh_action;
   fin.t_plus1 = actor_t_plus1(a, s);
   fin.acts_roll = io.acts_roll; fin.values_roll = io.values_roll; fin.logp_roll = io.logp_roll; fin.action = io.action;
   fin.mean = io.mean; fin.stdv = io.stdv; fin.ent = io.ent; fin.value = io.value;
@@ -2269,7 +2280,8 @@ static StepRoute step_route(const v4l_actor* a, int shared_encoder) {
   if (both([](const v4l_net_cfg& c) { return c.kind == V4L_NET_MLP && mlp_256(c) && head_256(c); }) && pf->enc[0].Kp <= 128) {
     const bool one_block = is_half(p.compute) && a->E <= 64 && p.out_dim <= 16 && pf->enc[0].Kp == 128 && pf->enc[0].pkf >= 0 &&
                            frag_heads();
-    return one_block && !tanh_pol ? StepRoute::MLP_ONE_BLOCK : StepRoute::MLP_PER_SAMPLE;
+    // a V4L_LOGSTD_HEAD policy (sigma per row, from the head output) goes the same way: rollout_mlp2_kernel keeps one sigma per column
+    return one_block && !tanh_pol && !pf->sd() ? StepRoute::MLP_ONE_BLOCK : StepRoute::MLP_PER_SAMPLE;
   }
   const bool dense_cnn = both([](const v4l_net_cfg& c) {
     if (!(head_256(c) && depth_64(c) && c.out_dim <= 16 && is_half(c.compute))) return false;
@@ -2477,7 +2489,7 @@ static int run_actor_mlp2(v4l_actor* a, const StepIO& io, hipStream_t s) {
 }
 
 // state-only MLP nets of the shipped shape: one launch per env step (rollout_mlp_kernel)
-template <typename T, int ACT>
+template <typename T, int ACT, bool SD = false>
 static int run_actor_fused_mlp(v4l_actor* a, const StepIO& io, hipStream_t s) {
   v4l_net *pf = a->pf, *vf = a->vf;
   const int E = a->E;
@@ -2501,7 +2513,7 @@ static int run_actor_fused_mlp(v4l_actor* a, const StepIO& io, hipStream_t s) {
   head(hd.n[1], vf, vk, ws_vf + Lv.out);
   const InfFinish fin = step_finish(a, io, s);
   g_op = "step";
-  V4L_KLAUNCH("rollout_mlp", 2.0 * 2 * E * (128.0 * 256 + 4 * 256 * 256), s, (rollout_mlp_kernel<T, ACT>), dim3(E, 2), dim3(1024), 0, s,
+  V4L_KLAUNCH("rollout_mlp", 2.0 * 2 * E * (128.0 * 256 + 4 * 256 * 256), s, (rollout_mlp_kernel<T, ACT, SD>), dim3(E, 2), dim3(1024), 0, s,
               (const ActCtl*)a->ctl, io.obs, E, en, hd, fin, io.state_roll);
   V4L_LAUNCH_CHECK();
   return 0;
@@ -2630,6 +2642,13 @@ static int launch_actor_loss(hipStream_t s, const ActorArgs& aa, dim3 blk) {
   return 0;
 }
 
+// the same for a V4L_LOGSTD_HEAD policy (actor_loss_sd_kernel: sigma per row, d(raw log sigma) in the d(out) row)
+static int launch_actor_loss_sd(hipStream_t s, const ActorArgs& aa, dim3 blk) {
+  if (aa.tanh_action) V4L_KLAUNCH("actor_loss", 0, s, actor_loss_sd_kernel<true>, dim3(1), blk, 0, s, aa);
+  else V4L_KLAUNCH("actor_loss", 0, s, actor_loss_sd_kernel<false>, dim3(1), blk, 0, s, aa);
+  return 0;
+}
+
 // V-MPO: the row selection and the single-block loss launch (csrc/elem.h)
 static int launch_vmpo_select(hipStream_t s, const float* adv, const int* rowidx, int n, int* sel) {
   g_op = "select";
@@ -2658,7 +2677,9 @@ static int launch_a2c_loss(hipStream_t s, const ActorArgs& aa, const UpdCtl* ctl
 extern "C" {
 
 const char* v4l_last_error(void) { return v4l::last_error(); }
-int v4l_version(void) { return 112; }  // A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
+// 113: v4l_net_cfg.has_logstd = V4L_LOGSTD_HEAD (GaussianContPolicy, continuous_policy.py:222-236: log sigma from the head's last layer, per row) —
+// actor_loss_sd_kernel, the per-row sampling epilogues of rollout_mlp_kernel / act_finish_sd_kernel, v4l_gauss_head_sd
+int v4l_version(void) { return 113; }  // 112: A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
 int v4l_abi_sizeof(int which) {
   return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) :
          which == 4 ? (int)sizeof(v4l_vmpo_hyper) : -1;  // (3 stays unassigned)
@@ -2897,6 +2918,17 @@ int v4l_gauss_head_tanh(const float* meanp_dev, const float* logstd_dev, const f
   V4L_LAUNCH_CHECK();
   return 0;
 }
+int v4l_gauss_head_sd(const float* out_dev, const float* acts_dev, const float* pre_tanh_dev, int n, int A, int tanh_action,
+                      float* mean_dev, float* std_dev, float* logstd_c_dev, float* ent_dev, float* logp_dev, void* stream) {
+  V4L_REQUIRE(out_dev && mean_dev && std_dev && logstd_c_dev && ent_dev && n > 0, "v4l_gauss_head_sd: bad argument");
+  V4L_REQUIRE(A > 0 && 2 * A <= OUT_LD, "v4l_gauss_head_sd: 1<=A<=%d (mean and log sigma share the %d-column head row) required, got %d",
+              OUT_LD / 2, OUT_LD, A);
+  V4L_REQUIRE(acts_dev == nullptr || logp_dev != nullptr, "v4l_gauss_head_sd: logp_dev is null");
+  hipLaunchKernelGGL(gauss_head_sd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, out_dev, acts_dev, n, A, mean_dev,
+                     std_dev, logstd_c_dev, ent_dev, logp_dev, tanh_action ? 1 : 0, pre_tanh_dev);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
 int v4l_col0(const float* src_dev, int n, float* dst_dev, void* stream) {
   V4L_REQUIRE(src_dev && dst_dev && n > 0, "v4l_col0: bad argument");
   hipLaunchKernelGGL(col0_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, src_dev, n, dst_dev);
@@ -3018,7 +3050,7 @@ int64_t v4l_prof_collect(char* buf, int64_t cap) {
 // ------------------------------------------------------------------------------------------ actor (rollout step)
 int v4l_actor_create(v4l_net* pf, v4l_net* vf, int E, v4l_actor** out) {
   V4L_REQUIRE(pf && vf && out && E > 0, "v4l_actor_create: bad argument");
-  V4L_REQUIRE(pf->cfg.has_logstd && vf->cfg.out_dim == 1 && pf->cfg.kind == vf->cfg.kind &&
+  V4L_REQUIRE(pf->cfg.has_logstd && !vf->cfg.has_logstd && vf->cfg.out_dim == 1 && pf->cfg.kind == vf->cfg.kind &&
                   pf->cfg.compute == vf->cfg.compute && pf->cfg.state_dim == vf->cfg.state_dim &&
                   pf->cfg.n_enc_hidden == vf->cfg.n_enc_hidden && pf->cfg.activation == vf->cfg.activation,
               "v4l_actor_create: pf must be a Gaussian policy and vf a value net of the same kind/compute/shape/activation");
@@ -3108,6 +3140,9 @@ static int run_actor_step(v4l_actor* a, const StepIO& io, int shared_encoder, hi
     case StepRoute::MLP_PER_SAMPLE:
       return by_compute(compute, [&](auto tag) -> int {
         typedef typename decltype(tag)::type T;
+        if (pf->sd())  // (sigma from the head row: instantiations of their own, the others are the code they were)
+          return pf->cfg.activation == V4L_ACT_TANH ? run_actor_fused_mlp<T, V4L_ACT_TANH, true>(a, io, s)
+                                                    : run_actor_fused_mlp<T, V4L_ACT_RELU, true>(a, io, s);
         return pf->cfg.activation == V4L_ACT_TANH ? run_actor_fused_mlp<T, V4L_ACT_TANH>(a, io, s)
                                                   : run_actor_fused_mlp<T, V4L_ACT_RELU>(a, io, s);
       });
@@ -3173,6 +3208,11 @@ static int run_actor_step(v4l_actor* a, const StepIO& io, int shared_encoder, hi
     if ((rc = fwd(vf, ws_vf, s, nullptr, 0))) return rc;
   }
   g_op = "sample";
+  if (pf->sd())
+    V4L_KLAUNCH("act_finish", 0, s, act_finish_sd_kernel, dim3(1), dim3(256), 0, s, a->ctl, ws_pf + pf->layout(E).out,
+                ws_vf + vf->layout(E).out, io.eps, E, pf->act_dim(), io.acts_roll, io.values_roll, io.logp_roll, io.action, io.mean,
+                io.stdv, io.ent, io.value, pf->cfg.tanh_action);
+  else
   V4L_KLAUNCH("act_finish", 0, s, act_finish_kernel, dim3(1), dim3(256), 0, s, a->ctl, ws_pf + pf->layout(E).out,
               pf->p[pf->logstd], ws_vf + vf->layout(E).out, io.eps, E, pf->cfg.out_dim, io.acts_roll, io.values_roll, io.logp_roll,
               io.action, io.mean, io.stdv, io.ent, io.value, pf->cfg.tanh_action);
@@ -3238,6 +3278,21 @@ static bool actor_takes_split(const v4l_actor* a, int shared_encoder) {
   const StepRoute r = step_route(a, shared_encoder);
   return r == StepRoute::CNN_DENSE || r == StepRoute::STACK_TOK16 || r == StepRoute::STACK_TOK17;
 }
+// introspection for tests: the name of the route step_route picks for this actor (the state-MLP kernels share one profiler label)
+const char* v4l_actor_route(const v4l_actor* a, int shared_encoder) {
+  if (a == nullptr) return "";
+  switch (step_route(a, shared_encoder)) {
+    case StepRoute::MLP_ONE_BLOCK: return "MLP_ONE_BLOCK";
+    case StepRoute::MLP_PER_SAMPLE: return "MLP_PER_SAMPLE";
+    case StepRoute::CNN_DENSE: return "CNN_DENSE";
+    case StepRoute::CNN_PER_SAMPLE: return "CNN_PER_SAMPLE";
+    case StepRoute::STACK_TOK16: return "STACK_TOK16";
+    case StepRoute::STACK_TOK17: return "STACK_TOK17";
+    case StepRoute::STACK_F32ENC: return "STACK_F32ENC";
+    case StepRoute::GENERAL: return "GENERAL";
+  }
+  return "";
+}
 int v4l_actor_split_supported(const v4l_actor* a, int shared_encoder) {
   return (a && a->bound && actor_takes_split(a, shared_encoder)) ? 1 : 0;
 }
@@ -3280,7 +3335,7 @@ int v4l_actor_step_rows(v4l_actor* a, const double* rows_host, int64_t ld, float
   const int64_t img = (int64_t)c.in_channels * c.img_hw * c.img_hw;
   int rc = v4l_host_cast_rows(rows_host, ld, a->E, c.state_dim, img, proprio_pinned, image16_pinned, c.compute, threads);
   if (rc) return rc;
-  const int na = a->E * c.out_dim, nv = a->E;
+  const int na = a->E * a->pf->act_dim(), nv = a->E;
   const bool poll = poll_seconds > 0.0;
   if (poll) {  // armed: a number in every slot means every (env, net) block has written its output, i.e. finished reading the rows
     const float nan = __builtin_nanf("");
@@ -3304,8 +3359,11 @@ int v4l_actor_step_rows(v4l_actor* a, const double* rows_host, int64_t ld, float
 // ------------------------------------------------------------------------------------------ trainer
 int v4l_trainer_create(v4l_net* pf, v4l_net* vf, v4l_net* target_pf, v4l_trainer** out) {
   V4L_REQUIRE(pf && vf && target_pf && out, "v4l_trainer_create: null argument");
-  V4L_REQUIRE(pf->cfg.has_logstd && target_pf->cfg.has_logstd && !vf->cfg.has_logstd && vf->cfg.out_dim == 1,
-              "v4l_trainer_create: pf/target_pf must be Gaussian policies and vf a scalar value net");
+  // (a policy / target pair with a logstd parameter each, or V4L_LOGSTD_HEAD each: GaussianContPolicy, continuous_policy.py:222-236)
+  V4L_REQUIRE(pf->cfg.has_logstd && pf->cfg.has_logstd == target_pf->cfg.has_logstd && !vf->cfg.has_logstd && vf->cfg.out_dim == 1,
+              "v4l_trainer_create: pf/target_pf must be Gaussian policies of one kind (a logstd parameter each, or "
+              "V4L_LOGSTD_HEAD each) and vf a scalar value net");
+  V4L_REQUIRE(pf->cfg.out_dim == target_pf->cfg.out_dim, "v4l_trainer_create: pf and target_pf disagree on out_dim");
   V4L_REQUIRE(pf->cfg.compute == vf->cfg.compute && pf->cfg.compute == target_pf->cfg.compute &&
                   pf->cfg.kind == vf->cfg.kind && pf->cfg.kind == target_pf->cfg.kind &&
                   pf->cfg.state_dim == vf->cfg.state_dim && pf->total_params == target_pf->total_params &&
@@ -3441,6 +3499,8 @@ static int check_update_args(const v4l_trainer* tr, const v4l_rollout* ro, int n
   V4L_REQUIRE(tr->pf->cfg.kind == V4L_NET_MLP || ro->image_dev, "v4l_trainer: rollout image array missing");
   V4L_REQUIRE(!hp->clipped_value_loss || ro->values_dev, "v4l_trainer: clipped_value_loss needs values_dev");
   V4L_REQUIRE(hp->world_size >= 1, "v4l_trainer: world_size must be >= 1");
+  V4L_REQUIRE(!tr->pf->sd() || (hp->world_size == 1 && tr->comm == nullptr),
+              "v4l_trainer: a V4L_LOGSTD_HEAD policy (GaussianContPolicy) runs in a single process");
   if (int rc = check_hyper(hp)) return rc;
   V4L_REQUIRE(tr->comm == nullptr || hp->world_size == tr->comm_world,
               "v4l_trainer: hyper.world_size (%d) differs from the communicator's (%d)", hp->world_size, tr->comm_world);
@@ -3607,13 +3667,21 @@ int v4l_trainer_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const
   g_op = "loss";
   {
     ActorArgs aa;
-    aa.mean = tr->ws + Lp.out; aa.logstd = pf->p[pf->logstd];
-    aa.tmean = stored ? nullptr : ws_t + Lt.out; aa.tlogstd = stored ? nullptr : tp->p[tp->logstd];
+    const bool sd = pf->sd();  // log sigma from the head row: no logstd parameter, its gradient leaves in the d(out) row
+    aa.mean = tr->ws + Lp.out; aa.logstd = sd ? nullptr : pf->p[pf->logstd];
+    aa.tmean = stored ? nullptr : ws_t + Lt.out; aa.tlogstd = stored || sd ? nullptr : tp->p[tp->logstd];
     aa.logp_old = ro->logp_old_dev; aa.acts = ro->acts_dev; aa.adv = ro->advs_dev; aa.rowidx = rowidx;
-    aa.n = n; aa.A = pf->cfg.out_dim; aa.inv_n = inv_n; aa.clip = hp->clip_para; aa.ent_coef = hp->entropy_coeff;
-    aa.dmean = tr->ws + Lp.dout; aa.dlogstd = tr->g_pf + pf->params[pf->logstd].goff; aa.st = st;
+    aa.n = n; aa.A = pf->act_dim(); aa.inv_n = inv_n; aa.clip = hp->clip_para; aa.ent_coef = hp->entropy_coeff;
+    aa.dmean = tr->ws + Lp.dout; aa.dlogstd = sd ? nullptr : tr->g_pf + pf->params[pf->logstd].goff; aa.st = st;
     aa.tanh_action = pf->cfg.tanh_action;
     aa.gscale = v4l_net_grad_scale(pf, n);
+    if (sd) {  // (V4L_NET_MLP: neither the fused forward-loss-backward launch nor the heads' chain beside the statistics)
+      const dim3 blk(n >= 512 ? 1024 : 256);
+      if ((rc = launch_actor_loss_sd(s, aa, blk))) return rc;
+      V4L_LAUNCH_CHECK();
+      PhaseScope ps("pf.bwd");
+      return v4l_net_backward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, tr->g_pf, stream);
+    }
     if (fb) {
       FbLoss lo;
       memset(&lo, 0, sizeof(lo));
@@ -3704,6 +3772,8 @@ int v4l_trainer_vmpo_set_state(v4l_trainer* tr, const double* in, void* stream) 
 static int check_vmpo_args(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp) {
   int rc = check_update_args(tr, ro, n, hp);
   if (rc) return rc;
+  V4L_REQUIRE(!tr->pf->sd(), "v4l_trainer_vmpo: a V4L_LOGSTD_HEAD policy (GaussianContPolicy) runs under the PPO update only: the V-MPO "
+              "loss kernel takes one log sigma per action column");
   V4L_REQUIRE(tr->vmpo != nullptr, "v4l_trainer_vmpo_actor_grads: no V-MPO state (v4l_trainer_vmpo_init)");
   V4L_REQUIRE(n <= tr->vmpo_n_max, "v4l_trainer_vmpo_actor_grads: n = %d is over the V-MPO block's n_max = %d", n, tr->vmpo_n_max);
   V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_vmpo_actor_grads: V-MPO runs in a single process");
@@ -4101,6 +4171,8 @@ static int check_a2c_args(const v4l_trainer* tr, const v4l_rollout* ro, int n, c
   int rc = check_update_args(tr, ro, n, hp);
   if (rc) return rc;
   V4L_REQUIRE(astats_all_dev != nullptr, "v4l_trainer_a2c: the A2C record array is missing");
+  V4L_REQUIRE(!tr->pf->sd(), "v4l_trainer_a2c: a V4L_LOGSTD_HEAD policy (GaussianContPolicy) runs under the PPO update only: the A2C loss "
+              "kernel takes one log sigma per action column");
   V4L_REQUIRE(tr->pf->cfg.kind == V4L_NET_MLP && tr->vf->cfg.kind == V4L_NET_MLP,
               "v4l_trainer_a2c: A2C runs state-MLP nets (V4L_NET_MLP) only: the reference's A2C raises on a shared encoder");
   V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_a2c: A2C runs in a single process");

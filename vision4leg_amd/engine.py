@@ -111,6 +111,9 @@ class HipNet:
     self.kind = cfg.kind
     self.compute = cfg.compute
     self.out_dim = cfg.out_dim
+    # GaussianContPolicy (continuous_policy.py:222-236): the head row is [mean | raw log sigma]; act_dim is A, out_dim the row's width
+    self.logstd_head = cfg.has_logstd == _lib.V4L_LOGSTD_HEAD
+    self.act_dim = cfg.out_dim // 2 if self.logstd_head else cfg.out_dim
     self.state_dim = cfg.state_dim
     self.img_elems = 0 if cfg.kind == V4L_NET_MLP else cfg.in_channels * cfg.img_hw * cfg.img_hw
     self.Sp = self.L.v4l_net_state_ld(h)
@@ -324,16 +327,21 @@ class HipNet:
     return self.gauss_head(out, logstd, n, acts, tanh_action=tanh_action)
 
   def gauss_head(self, out, logstd, n, acts=None, tanh_action=False, pre_tanh=None):
-    A, dev = self.out_dim, out.device
+    A, dev = self.act_dim, out.device
     mean = torch.empty(n, A, dtype=torch.float32, device=dev)
     std = torch.empty(n, A, dtype=torch.float32, device=dev)
-    lsc = torch.empty(A, dtype=torch.float32, device=dev)
+    lsc = torch.empty((n, A) if self.logstd_head else (A,), dtype=torch.float32, device=dev)
     ent = torch.empty(n, dtype=torch.float32, device=dev)
     logp = None
     if acts is not None:
       acts = acts.reshape(n, A).contiguous().float()
       logp = torch.empty(n, dtype=torch.float32, device=dev)
-    if tanh_action:  # TanhNormal.log_prob (policies/distribution.py:38-51)
+    if self.logstd_head:  # sigma per row, from the head output itself (logstd is None)
+      if pre_tanh is not None:
+        pre_tanh = pre_tanh.reshape(n, A).contiguous().float()
+      check(self.L.v4l_gauss_head_sd(_ptr(out), _ptr(acts), _ptr(pre_tanh), n, A, int(bool(tanh_action)), _ptr(mean), _ptr(std),
+                                     _ptr(lsc), _ptr(ent), _ptr(logp), _stream()), "v4l_gauss_head_sd")
+    elif tanh_action:  # TanhNormal.log_prob (policies/distribution.py:38-51)
       if pre_tanh is not None:
         pre_tanh = pre_tanh.reshape(n, A).contiguous().float()
       check(self.L.v4l_gauss_head_tanh(_ptr(out), _ptr(logstd), _ptr(acts), _ptr(pre_tanh), n, A, _ptr(mean), _ptr(std),
@@ -716,7 +724,7 @@ class HipActor:
     h = C.c_void_p()
     check(self.L.v4l_actor_create(pf_net.h, vf_net.h, E, C.byref(h)), "v4l_actor_create")
     self.h = h
-    A = pf_net.out_dim
+    A = pf_net.act_dim
     self.ws = _buf(self.L.v4l_actor_ws_floats(h), torch.float32, dev)
     self.ctl = _buf(self.L.v4l_actor_ctl_bytes(h), torch.uint8, dev, zero=True)
     self.obs = torch.zeros(E, pf_net.state_dim + pf_net.img_elems, dtype=torch.float32, device=dev)
@@ -883,6 +891,10 @@ class HipActor:
           break
     torch.cuda.current_stream(self.device).synchronize()
     return a
+
+  def route(self):
+    """The kernel family a step of this actor runs on (include/v4l_hip.h v4l_actor_route): "MLP_ONE_BLOCK", "GENERAL", ..."""
+    return self.L.v4l_actor_route(self.h, int(self.shared_encoder)).decode()
 
   def split_supported(self):
     """True when this actor's step can take the observation split (v4l_actor_step_split): bf16 compute, an image net on the

@@ -39,6 +39,9 @@ def _is_state_mlp(net):
 class A2C(PPO):
     def __init__(self, pf, vf, plr=3e-4, vlr=3e-4, optimizer_class=optim.Adam, entropy_coeff=0.001, shuffle=True, tau=None, gae=True,
                  **kwargs):
+        if getattr(pf, "logstd_head", False):
+            raise NotImplementedError("vision4leg_amd: A2C does not take policies.GaussianContPolicy (log-std from the head): the "
+                                      "A2C loss kernel takes one log-std per action column; the policy runs under algo.PPO")
         if not (_is_state_mlp(pf) and _is_state_mlp(vf)):
             raise NotImplementedError("vision4leg_amd: A2C runs state-MLP nets (networks.Net pairs) only: the reference's A2C "
                                       "raises on a shared encoder (vf(obs) is evaluated before pf_optimizer.step() and "

@@ -195,6 +195,12 @@ class PPO:
         # torch.optim.Adam / AdamW, a functools.partial of either, or "Adam" / "AdamW" + optimizer_kwargs (JSON configs): resolved
         # the way the reference would build it, `optimizer_class(params, lr=..., eps=1e-5)` (a2c.py:30-40); anything else raises
         opt = hip_optim.resolve(optimizer_class, optimizer_kwargs, lr=plr)
+        if getattr(pf, "logstd_head", False):  # policies.GaussianContPolicy: before anything touches a device
+            forced = (os.environ.get("V4L_FORCE_DP_PHASES", "0") != "0" and torch.distributed.is_available()
+                      and torch.distributed.is_initialized())
+            if _dist_world() > 1 or forced:
+                raise NotImplementedError("vision4leg_amd: GaussianContPolicy (log-std from the head) runs in a single process: "
+                                          "its data-parallel update (world_size > 1 / V4L_FORCE_DP_PHASES) is not verified")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("vision4leg_amd: PPO needs a GPU device (got %s); there is no CPU path" % self.device)

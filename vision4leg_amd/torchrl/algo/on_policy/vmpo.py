@@ -40,6 +40,9 @@ class _ScalarAdam:
 
 class VMPO(PPO):
     def __init__(self, pf, vf, opt_epochs=10, eta_eps=0.02, alpha_eps=0.1, clipped_value_loss=False, **kwargs):
+        if getattr(pf, "logstd_head", False):
+            raise NotImplementedError("vision4leg_amd: VMPO does not take policies.GaussianContPolicy (log-std from the head): the "
+                                      "V-MPO loss kernel takes one log-std per action column; the policy runs under algo.PPO")
         if kwargs.get("skip_nonfinite_steps"):
             raise NotImplementedError("vision4leg_amd: VMPO does not take skip_nonfinite_steps=True (the guard covers PPO's two "
                                       "optimisers, not eta / alpha)")

@@ -171,7 +171,7 @@ class VecOnPolicyCollector:
             if buf._net is None:  # PPO.__init__ normally attaches it
                 buf.attach(self.pf.hip, self.device)
             self._actor = RolloutActor(self.pf, self.vf, self.env.env_nums)
-            self._actor.attach(buf.step_arrays(self.pf.hip.out_dim))
+            self._actor.attach(buf.step_arrays(self.pf.hip.act_dim))
         return self._actor
 
     # ---- one vectorised env step -----------------------------------------------------------------------------------

@@ -145,6 +145,8 @@ class Net(_HipNetMixin, nn.Module):
         c.n_enc_hidden = _fill_hidden(c.enc_hidden, self.base.hidden_shapes, "base hidden")
         c.n_head_hidden = _fill_hidden(c.head_hidden, self.append_hidden_shapes, "append hidden")
         c.has_logstd = int(hasattr(self, "logstd"))
+        if getattr(self, "logstd_head", False):  # policies.GaussianContPolicy (continuous_policy.py:222-236): [mean | raw log sigma]
+            c.has_logstd = _lib.V4L_LOGSTD_HEAD
         return c
 
 

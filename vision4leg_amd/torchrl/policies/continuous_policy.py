@@ -1,9 +1,10 @@
 """Gaussian policies of the PPO hot path with the reference's names and method protocol
-(torchrl/policies/continuous_policy.py: GaussianContPolicyBase 77-146, ...BasicBias 239-254,
+(torchrl/policies/continuous_policy.py: GaussianContPolicyBase 77-146, GaussianContPolicy 222-236, ...BasicBias 239-254,
 ...NatureEncoderProj 257-272, ...ImpalaEncoderProj 275-290, ...Transformer 461-475, ...LocoTransformer 478-492).
 
 A policy is a top-level HIP net plus the state-independent `logstd` parameter. `forward/explore/eval_act/update`
-evaluate the trunk and the Gaussian head (clamp, exp, entropy, log-prob) with libv4l_hip.so kernels; only the
+evaluate the trunk and the Gaussian head (clamp, exp, entropy, log-prob) with libv4l_hip.so kernels (GaussianContPolicy has no
+`logstd` parameter: the second half of its head's last layer is the log sigma of the row, continuous_policy.py:222-236); only the
 random draw of `explore` uses torch's generator so that seeded rollouts consume the RNG stream exactly like
 the reference's `Normal(mean, std).sample()`.
 """
@@ -17,7 +18,7 @@ from .. import networks
 LOG_SIG_MAX = 2
 LOG_SIG_MIN = -5
 
-__all__ = ["LOG_SIG_MAX", "LOG_SIG_MIN", "GaussianContPolicyBase", "GaussianContPolicyBasicBias",
+__all__ = ["LOG_SIG_MAX", "LOG_SIG_MIN", "GaussianContPolicy", "GaussianContPolicyBase", "GaussianContPolicyBasicBias",
            "GaussianContPolicyImpalaEncoderProj", "GaussianContPolicyLocoTransformer",
            "GaussianContPolicyNatureEncoderProj", "GaussianContPolicyTransformer", "RolloutActor"]
 
@@ -85,7 +86,11 @@ class RolloutActor:
 
 
 class GaussianContPolicyBase:
-    """Mixin: needs `self.hip` (HipNet), `self.logstd`, `self.tanh_action`."""
+    """Mixin: needs `self.hip` (HipNet), `self.tanh_action` and `self.logstd` (or `logstd_head = True` instead of it)."""
+
+    def _logstd_data(self):
+        # GaussianContPolicy has no such parameter: the engine reads log sigma from the head row (HipNet.logstd_head)
+        return None if getattr(self, "logstd_head", False) else self.logstd.data
 
     def _init_policy(self, output_shape, tanh_action, log_init):
         self.continuous = True
@@ -95,7 +100,7 @@ class GaussianContPolicyBase:
     def _gaussian(self, x, actions=None):
         lead = x.shape[:-1]
         x2 = x.reshape(-1, x.shape[-1])
-        mean, std, log_std, ent, logp = self.hip.gaussian(x2, self.logstd.data, actions, tanh_action=self.tanh_action)
+        mean, std, log_std, ent, logp = self.hip.gaussian(x2, self._logstd_data(), actions, tanh_action=self.tanh_action)
         A = mean.shape[-1]
         mean, std = mean.view(*lead, A), std.view(*lead, A)
         ent = ent.view(*lead, 1)
@@ -127,8 +132,10 @@ class GaussianContPolicyBase:
             n = mean.numel() // A
             padded = torch.zeros(n, 16, dtype=torch.float32, device=mean.device)  # V4L_OUT_LD rows
             padded[:, :A] = mean.reshape(n, A)
+            if getattr(self, "logstd_head", False):  # [mean | log sigma] rows (clamping the clamped values again changes nothing)
+                padded[:, A:2 * A] = log_std.reshape(n, A)
             # tanh: dis.log_prob(action, pre_tanh_value=z) (continuous_policy.py:99-106) — the draw itself, not atanh(action)
-            *_, logp = self.hip.gauss_head(padded, self.logstd.data, n, action, tanh_action=self.tanh_action,
+            *_, logp = self.hip.gauss_head(padded, self._logstd_data(), n, action, tanh_action=self.tanh_action,
                                            pre_tanh=z if self.tanh_action else None)
             dic["log_prob"] = logp.view(*mean.shape[:-1], 1)
         dic["action"] = action.squeeze(0)
@@ -137,6 +144,33 @@ class GaussianContPolicyBase:
     def update(self, obs, actions):
         mean, std, log_std, ent, logp = self._gaussian(obs, actions)
         return {"mean": mean, "dis": Normal(mean, std), "log_std": log_std, "std": std, "log_prob": logp, "ent": ent}
+
+
+class GaussianContPolicy(networks.Net, GaussianContPolicyBase):
+    """The Gaussian policy whose log sigma is state dependent (reference continuous_policy.py:222-236): a networks.Net with
+    output_shape = 2 A; `x.chunk(2, -1)` of its output is (mean, log sigma), log sigma clamped to [-5, 2] per sample. No `logstd`
+    parameter: the state_dict keys are exactly networks.Net's. forward -> (mean [n, A], std [n, A], log_std [n, A]).
+    Runs under algo.PPO; the head row of the engine has 16 columns, so A = 1 .. 8."""
+
+    logstd_head = True  # read by Net._net_cfg -> v4l_net_cfg.has_logstd = V4L_LOGSTD_HEAD
+
+    def __init__(self, tanh_action=False, **kwargs):
+        width = int(kwargs["output_shape"])
+        if width < 2 or width % 2:
+            raise NotImplementedError("vision4leg_amd: GaussianContPolicy splits its output into mean and log-std halves: "
+                                      "output_shape must be even (2 * action dimensions), got %d" % width)
+        if width > 16:
+            raise NotImplementedError("vision4leg_amd: GaussianContPolicy takes output_shape <= 16 (8 action dimensions: mean "
+                                      "and log-std share the engine's 16-column head row), got %d" % width)
+        super().__init__(**kwargs)
+        self.continuous = True
+        self.tanh_action = bool(tanh_action)  # TanhNormal head (policies/distribution.py:5-80); read by _net_cfg -> v4l_net_cfg
+
+    def _gaussian(self, x, actions=None):
+        mean, std, log_std, ent, logp = super()._gaussian(x, actions)
+        return mean, std, log_std.view(mean.shape), ent, logp
+
+    forward = GaussianContPolicyBase.forward
 
 
 class GaussianContPolicyBasicBias(networks.Net, GaussianContPolicyBase):
