@@ -2673,6 +2673,25 @@ static int launch_a2c_loss(hipStream_t s, const ActorArgs& aa, const UpdCtl* ctl
   return 0;
 }
 
+// Captures what body() launches on s (thread-local mode) and instantiates it into *exec. A failed body ends the capture,
+// destroys what was recorded and returns the body's rc; otherwise the end-capture error decides.
+template <class Body>
+static int capture_graph(hipStream_t s, const char* what, Body&& body, hipGraphExec_t* exec) {
+  hipGraph_t graph = nullptr;
+  V4L_TRACE("%s: begin capture", what);
+  V4L_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  const int rc = body();
+  V4L_TRACE("%s: end capture rc=%d", what, rc);
+  const hipError_t e = hipStreamEndCapture(s, &graph);
+  if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+  V4L_HIP_CHECK(e);
+  V4L_TRACE("%s: instantiate", what);
+  V4L_HIP_CHECK(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
+  V4L_HIP_CHECK(hipGraphDestroy(graph));
+  V4L_TRACE("%s: instantiated", what);
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -3239,20 +3258,8 @@ static int actor_step_impl(v4l_actor* a, const StepIO& io, int shared_encoder, i
     memcpy(a->key, key, sizeof(key));
   }
   if (!a->warm) { a->warm = true; return run(); }
-  if (a->gexec == nullptr) {
-    hipGraph_t graph = nullptr;
-    V4L_TRACE("actor: begin capture");
-    V4L_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int rc = run();
-    V4L_TRACE("actor: end capture rc=%d", rc);
-    const hipError_t e = hipStreamEndCapture(s, &graph);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    V4L_HIP_CHECK(e);
-    V4L_TRACE("actor: instantiate");
-    V4L_HIP_CHECK(hipGraphInstantiate(&a->gexec, graph, nullptr, nullptr, 0));
-    V4L_HIP_CHECK(hipGraphDestroy(graph));
-    V4L_TRACE("actor: instantiated");
-  }
+  if (a->gexec == nullptr)
+    if (int rc = capture_graph(s, "actor", run, &a->gexec)) return rc;
   V4L_HIP_CHECK(hipGraphLaunch(a->gexec, s));
   if (a->dense_in_graph) ++a->dense_seq;  // the replayed rollout_dense_kernel advanced ctl->seq
   V4L_TRACE("actor: launched");
@@ -3956,14 +3963,7 @@ int v4l_trainer_comm_selftest(v4l_trainer* tr, int use_graph, int64_t* mismatche
   if ((rc = fill_and_reduce()) || (rc = check())) return rc;
   hipGraphExec_t exec = nullptr;
   if (use_graph) {
-    hipGraph_t graph = nullptr;
-    V4L_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    rc = fill_and_reduce();
-    const hipError_t e = hipStreamEndCapture(s, &graph);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    V4L_HIP_CHECK(e);
-    V4L_HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    V4L_HIP_CHECK(hipGraphDestroy(graph));
+    if ((rc = capture_graph(s, "comm selftest", fill_and_reduce, &exec))) return rc;
     hipError_t el = hipSuccess;
     for (int rep = 0; rep < 2 && !rc && el == hipSuccess; ++rep) {
       el = hipGraphLaunch(exec, s);
@@ -4016,20 +4016,9 @@ int v4l_trainer_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const
     tr->warm = true;
     return run_update(tr, ro, n, hp, stream);
   }
-  if (tr->gexec == nullptr) {
-    hipGraph_t graph = nullptr;
-    V4L_TRACE("update: begin capture");
-    V4L_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    rc = run_update(tr, ro, n, hp, stream);
-    V4L_TRACE("update: end capture rc=%d", rc);
-    const hipError_t e = hipStreamEndCapture(s, &graph);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    V4L_HIP_CHECK(e);
-    V4L_TRACE("update: instantiate");
-    V4L_HIP_CHECK(hipGraphInstantiate(&tr->gexec, graph, nullptr, nullptr, 0));
-    V4L_HIP_CHECK(hipGraphDestroy(graph));
-    V4L_TRACE("update: instantiated");
-  }
+  if (tr->gexec == nullptr &&
+      (rc = capture_graph(s, "update", [&]() { return run_update(tr, ro, n, hp, stream); }, &tr->gexec)))
+    return rc;
   V4L_HIP_CHECK(hipGraphLaunch(tr->gexec, s));
   V4L_TRACE("update: launched");
   return 0;
@@ -4058,17 +4047,14 @@ int v4l_trainer_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const 
     tr->gexec_run = nullptr;
   }
   if (tr->gexec_run == nullptr) {
-    hipGraph_t graph = nullptr;
-    V4L_TRACE("update run: begin capture of %d updates", count);
-    V4L_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    for (int u = 0; u < count && !rc; ++u) rc = run_update(tr, ro, n, hp, stream);
-    const hipError_t e = hipStreamEndCapture(s, &graph);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    V4L_HIP_CHECK(e);
-    V4L_HIP_CHECK(hipGraphInstantiate(&tr->gexec_run, graph, nullptr, nullptr, 0));
-    V4L_HIP_CHECK(hipGraphDestroy(graph));
+    V4L_TRACE("update run: %d updates", count);
+    auto run = [&]() {
+      int rb = 0;
+      for (int u = 0; u < count && !rb; ++u) rb = run_update(tr, ro, n, hp, stream);
+      return rb;
+    };
+    if ((rc = capture_graph(s, "update run", run, &tr->gexec_run))) return rc;
     tr->gexec_run_count = count;
-    V4L_TRACE("update run: instantiated");
   }
   V4L_HIP_CHECK(hipGraphLaunch(tr->gexec_run, s));
   return 0;
@@ -4266,18 +4252,14 @@ static void a2c_graph_key(const v4l_trainer* tr, const v4l_rollout* ro, int n, c
 // Captures `count` A2C updates on s into *exec
 static int capture_a2c(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev, int count,
                        hipStream_t s, hipGraphExec_t* exec) {
-  hipGraph_t graph = nullptr;
-  int rc = 0;
-  V4L_TRACE("a2c update: begin capture of %d update(s)", count);
-  V4L_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  for (int u = 0; u < count && !rc; ++u) rc = run_a2c_update(tr, ro, n, hp, astats_all_dev, (void*)s);
-  const hipError_t e = hipStreamEndCapture(s, &graph);
-  if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-  V4L_HIP_CHECK(e);
-  V4L_HIP_CHECK(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
-  V4L_HIP_CHECK(hipGraphDestroy(graph));
+  V4L_TRACE("a2c update: %d update(s)", count);
+  auto run = [&]() {
+    int rb = 0;
+    for (int u = 0; u < count && !rb; ++u) rb = run_a2c_update(tr, ro, n, hp, astats_all_dev, (void*)s);
+    return rb;
+  };
+  if (int rc = capture_graph(s, "a2c update", run, exec)) return rc;
   ++tr->a2c_captures;
-  V4L_TRACE("a2c update: instantiated");
   return 0;
 }
 int v4l_trainer_a2c_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,

@@ -657,11 +657,14 @@ class HipTrainer:
     self._count(int(count))
     self._after_steps()
 
+  def _graph_counts(self, entry):
+    cap, rep = C.c_int64(0), C.c_int64(0)
+    check(getattr(self.L, entry)(self.h, C.byref(cap), C.byref(rep)), entry)
+    return cap.value, rep.value
+
   def vmpo_graph_counts(self):
     """-> (V-MPO graphs instantiated, V-MPO graph replays launched) since this trainer was created."""
-    cap, rep = C.c_int64(0), C.c_int64(0)
-    check(self.L.v4l_trainer_vmpo_graph_counts(self.h, C.byref(cap), C.byref(rep)), "v4l_trainer_vmpo_graph_counts")
-    return cap.value, rep.value
+    return self._graph_counts("v4l_trainer_vmpo_graph_counts")
 
   # ---- A2C (torchrl/algo/on_policy/a2c.py:46-107) on state-MLP nets: two loss launches of its own between the phases above.
   # astats_all: [U][V4L_A2C_STATS] float32 device tensor of the open run's A2C records (zeroed by the caller)
@@ -697,9 +700,7 @@ class HipTrainer:
 
   def a2c_graph_counts(self):
     """-> (A2C graphs instantiated, A2C graph replays launched) since this trainer was created."""
-    cap, rep = C.c_int64(0), C.c_int64(0)
-    check(self.L.v4l_trainer_a2c_graph_counts(self.h, C.byref(cap), C.byref(rep)), "v4l_trainer_a2c_graph_counts")
-    return cap.value, rep.value
+    return self._graph_counts("v4l_trainer_a2c_graph_counts")
 
 
 def vmpo_select(adv, rowidx, n):
