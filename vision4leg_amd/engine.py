@@ -541,20 +541,19 @@ class HipTrainer:
     else:
       self._adam_steps = (self._adam_steps[0] + updates, self._adam_steps[1] + updates)
 
-  def update_next(self, ro, n, graph=True):
+  def _call_update(self, entry, ro, n, tail, updates):
+    """One library call that runs `updates` whole updates of the open run: entry(tr, ro, n, hp, *tail, stream)."""
     self._pre(n)
-    check(self.L.v4l_trainer_update_next(self.h, C.byref(ro), n, C.byref(self.hp), int(graph), _stream()),
-          "v4l_trainer_update_next")
-    self._count(1)
+    check(getattr(self.L, entry)(self.h, C.byref(ro), n, C.byref(self.hp), *tail, _stream()), entry)
+    self._count(updates)
     self._after_steps()
+
+  def update_next(self, ro, n, graph=True):
+    self._call_update("v4l_trainer_update_next", ro, n, (int(graph),), 1)
 
   def update_run(self, ro, n, count, graph=True):
     """The next `count` updates behind one begin(): with graph=True ONE hipGraph replay for all of them (v4l_trainer_update_run)."""
-    self._pre(n)
-    check(self.L.v4l_trainer_update_run(self.h, C.byref(ro), n, C.byref(self.hp), int(count), int(graph), _stream()),
-          "v4l_trainer_update_run")
-    self._count(int(count))
-    self._after_steps()
+    self._call_update("v4l_trainer_update_run", ro, n, (int(count), int(graph)), int(count))
 
   def update(self, ro, rowidx, n, lr_pf, lr_vf, stats, skip=None):
     """One eager PPO.update on minibatch rows rowidx (int32 device tensor or None); stats: [V4L_STATS] floats; skip: None, or
@@ -593,7 +592,10 @@ class HipTrainer:
   def vmpo_init(self, eta_eps=0.02, alpha_eps=0.1, eta0=1.0, alpha0=0.1, lr_scale=1.0):
     """VMPO.__init__'s two learnable scalars and their optimiser state (v_mpo.py:27-39) in a device block this trainer owns,
     next to the rows vmpo_actor_grads selects. lr_scale=0 (tests): the scalars and their optimiser state stay as they are."""
-    vhp = _lib.VMPOHyper(float(eta_eps), float(alpha_eps), float(eta0), float(alpha0), float(lr_scale))
+    self._vmpo_bind(_lib.VMPOHyper(float(eta_eps), float(alpha_eps), float(eta0), float(alpha0), float(lr_scale)))
+
+  def _vmpo_bind(self, vhp):
+    """A zeroed device block for self.batch rows, initialised from vhp."""
     block = _buf(self.L.v4l_trainer_vmpo_bytes(self.h, self.batch), torch.uint8, self.device, zero=True)
     check(self.L.v4l_trainer_vmpo_init(self.h, C.byref(vhp), _ptr(block), self.batch, _stream()), "v4l_trainer_vmpo_init")
     self._vmpo = (vhp, block)
@@ -601,10 +603,7 @@ class HipTrainer:
   def _vmpo_regrow(self):
     """The workspace grew (a larger minibatch): a block for that many rows, eta / alpha and their optimiser state carried over."""
     state = self.vmpo_state()
-    vhp = self._vmpo[0]
-    block = _buf(self.L.v4l_trainer_vmpo_bytes(self.h, self.batch), torch.uint8, self.device, zero=True)
-    check(self.L.v4l_trainer_vmpo_init(self.h, C.byref(vhp), _ptr(block), self.batch, _stream()), "v4l_trainer_vmpo_init")
-    self._vmpo = (vhp, block)
+    self._vmpo_bind(self._vmpo[0])
     self.vmpo_set_state(state)
 
   def vmpo_state(self):
@@ -639,11 +638,7 @@ class HipTrainer:
     has run; graph=False: eager launches."""
     if self._vmpo is None:
       raise RuntimeError("vision4leg_amd: vmpo_init() first")
-    self._pre(n)
-    check(self.L.v4l_trainer_vmpo_update_next(self.h, C.byref(ro), n, C.byref(self.hp), _ptr(vstats_all), int(graph), _stream()),
-          "v4l_trainer_vmpo_update_next")
-    self._count(1)
-    self._after_steps()
+    self._call_update("v4l_trainer_vmpo_update_next", ro, n, (_ptr(vstats_all), int(graph)), 1)
 
   def vmpo_update_run(self, ro, n, count, vstats_all, graph=True):
     """The next `count` V-MPO updates behind one begin(): with graph=True ONE hipGraph replay for all of them
@@ -651,11 +646,7 @@ class HipTrainer:
     is keyed on them."""
     if self._vmpo is None:
       raise RuntimeError("vision4leg_amd: vmpo_init() first")
-    self._pre(n)
-    check(self.L.v4l_trainer_vmpo_update_run(self.h, C.byref(ro), n, C.byref(self.hp), _ptr(vstats_all), int(count), int(graph),
-                                             _stream()), "v4l_trainer_vmpo_update_run")
-    self._count(int(count))
-    self._after_steps()
+    self._call_update("v4l_trainer_vmpo_update_run", ro, n, (_ptr(vstats_all), int(count), int(graph)), int(count))
 
   def _graph_counts(self, entry):
     cap, rep = C.c_int64(0), C.c_int64(0)
@@ -682,21 +673,13 @@ class HipTrainer:
   def a2c_update_next(self, ro, n, astats_all, graph=False):
     """The next A2C minibatch update of the run begin() opened (v4l_trainer_a2c_update_next). graph=True: one hipGraph replay
     once the configuration has run; graph=False: eager launches."""
-    self._pre(n)
-    check(self.L.v4l_trainer_a2c_update_next(self.h, C.byref(ro), n, C.byref(self.hp), _ptr(astats_all), int(graph), _stream()),
-          "v4l_trainer_a2c_update_next")
-    self._count(1)
-    self._after_steps()
+    self._call_update("v4l_trainer_a2c_update_next", ro, n, (_ptr(astats_all), int(graph)), 1)
 
   def a2c_update_run(self, ro, n, count, astats_all, graph=True):
     """The next `count` A2C updates behind one begin(): with graph=True ONE hipGraph replay for all of them
     (v4l_trainer_a2c_update_run). Keep the row-index, record and astats_all tensors at one address from run to run: the graph is
     keyed on them."""
-    self._pre(n)
-    check(self.L.v4l_trainer_a2c_update_run(self.h, C.byref(ro), n, C.byref(self.hp), _ptr(astats_all), int(count), int(graph),
-                                            _stream()), "v4l_trainer_a2c_update_run")
-    self._count(int(count))
-    self._after_steps()
+    self._call_update("v4l_trainer_a2c_update_run", ro, n, (_ptr(astats_all), int(count), int(graph)), int(count))
 
   def a2c_graph_counts(self):
     """-> (A2C graphs instantiated, A2C graph replays launched) since this trainer was created."""

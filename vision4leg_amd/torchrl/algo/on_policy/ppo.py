@@ -579,16 +579,17 @@ class PPO:
                     infos = self.update(batch)
                     self.logger.add_update_info(infos)
 
+    def _epoch_rowidx(self, passes):
+        """The row lists of all minibatches of an epoch, `passes` times over the samples -> int32 [U][n] device tensor."""
+        batches = [b["rowidx"] for _ in range(passes)
+                   for b in self.replay_buffer.one_iteration(self.batch_size, self.sample_key, self.shuffle)]
+        return torch.from_numpy(np.stack(batches)).to(self.device)  # one upload per epoch
+
     def _update_epoch_resident(self):
-        buf = self.replay_buffer
-        state, image, acts, advs, rets, vals, logp = buf.device_rollout()
+        state, image, acts, advs, rets, vals, logp = self.replay_buffer.device_rollout()
         ro = HipTrainer.rollout(state, image, acts, advs, rets, vals, logp)
-        batches = []
-        for _ in range(self.opt_epochs):
-            for b in buf.one_iteration(self.batch_size, self.sample_key, self.shuffle):
-                batches.append(b["rowidx"])
-        rowidx = torch.from_numpy(np.stack(batches)).to(self.device)  # one upload per epoch
-        U = len(batches)
+        rowidx = self._epoch_rowidx(self.opt_epochs)
+        U = len(rowidx)
         stats = torch.zeros(U, _lib.V4L_STATS, dtype=torch.float32, device=self.device)
         self.run_updates(ro, rowidx, stats)
         flags = None
@@ -687,26 +688,28 @@ class PPO:
         tr.bucket_tail(0, 0, self.world_size)
         tr.actor_step()
 
-    def update(self, batch):
-        """One minibatch update from a reference-style host batch (ppo.py:125-153). Returns the 18-key info."""
+    def _upload_batch(self, batch, keys):
+        """A reference-style host batch onto the device: batch["obs"] ingested into the staging rollout `_stage` ((re)allocated
+        for its row count), batch[k] for k in keys as fresh float32 tensors ("acts" [n][A], the others [n]). -> n, those tensors."""
         if "rowidx" in batch:
             raise RuntimeError("device-resident batches are consumed by update_per_epoch")
-        self.training_update_num += 1
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
+        obs = up(batch["obs"])
+        n = obs.shape[0]
+        net = self.pf.hip
+        net.ensure_bound()
+        if self._stage is None or self._stage[0].shape[0] != n:
+            self._stage = net.alloc_rollout(n, self.device)
+        net.ingest(obs, self._stage[0], self._stage[1])
+        return n, [up(batch[k]).reshape((n, -1) if k == "acts" else n) for k in keys]
+
+    def update(self, batch):
+        """One minibatch update from a reference-style host batch (ppo.py:125-153). Returns the 18-key info."""
         dev = self.device
         with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-            obs = up(batch["obs"])
-            n = obs.shape[0]
-            net = self.pf.hip
-            net.ensure_bound()
-            if self._stage is None or self._stage[0].shape[0] != n:
-                self._stage = net.alloc_rollout(n, dev)
-            net.ingest(obs, self._stage[0], self._stage[1])
-            acts = up(batch["acts"]).reshape(n, -1)
-            advs = up(batch["advs"]).reshape(n)
-            rets = up(batch["estimate_returns"]).reshape(n)
-            vals = up(batch["values"]).reshape(n)
-            ro = HipTrainer.rollout(self._stage[0], self._stage[1], acts, advs, rets, vals)
+            n, arrays = self._upload_batch(batch, ("acts", "advs", "estimate_returns", "values"))
+            self.training_update_num += 1
+            ro = HipTrainer.rollout(self._stage[0], self._stage[1], *arrays)
             stats = torch.zeros(1, _lib.V4L_STATS, dtype=torch.float32, device=dev)
             skip = torch.zeros(1, 2, dtype=torch.int32, device=dev) if self.skip_nonfinite_steps else None
             tr = self.trainer
