@@ -502,6 +502,40 @@ int v4l_trainer_a2c_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, co
 /* A2C graphs instantiated and hipGraphLaunch calls made by the two entries above since the trainer was created */
 int v4l_trainer_a2c_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays);
 
+/* ---- REINFORCE minibatch update (version 114): replaces Reinforce.update (torchrl/algo/on_policy/reinforce.py:34-76) for every
+ * net kind the PPO update takes. No critic: the reference's Reinforce holds a ZeroNet as vf; here the trainer's vf is a critic
+ * whose last layer is zero (networks.zero_critic), which the rollout step and the return estimate run and no launch of an
+ * update reads or writes. One update is: the opening launch (row selection, advantage statistics and the POLICY's operand-type
+ * weight copies in one launch, begin_pack_kernel on pf's packs), the policy's forward, the REINFORCE loss launch, the policy's
+ * backward, v4l_trainer_actor_step (it closes the update). The critic's Adam step count never advances. max_grad_norm,
+ * entropy_coeff and eps are the caller's v4l_ppo_hyper's (reinforce.py:26-29,65: 0.5, Adam's default eps 1e-8). Single process
+ * only, no guard array (v4l_trainer_begin_guarded), no V4L_LOGSTD_HEAD policy. ---- */
+#define V4L_REINFORCE_STATS 12 /* floats per update in the REINFORCE record; [0..9] = the 10 keys of reinforce.py:43-74 in that
+                                  order: advs/mean, std, max, min, Training/policy_loss, ent, logprob/mean, std, max, min; the
+                                  rest stays as the caller cleared it. advs/std is the POPULATION std (the reference logs
+                                  numpy's std() of the host batch, reinforce.py:44); the PPO record keeps torch's */
+/* reinforce.py:52-63 up to policy_loss.backward(): the opening launch through the policy's backward into its gradient buffer;
+ * nothing is stepped (v4l_trainer_actor_step follows). rstats_all_dev: [U][V4L_REINFORCE_STATS] records of the run opened by
+ * v4l_trainer_begin (row = the update's index), not NULL. policy_loss = mean(-log_prob * an) - entropy_coeff * ent with
+ * an = (a - mean) / (std + 1e-5) from the minibatch statistics; logprob/std is unbiased over n. Fills the PPO record's advantage
+ * statistics, policy_loss and logprob/mean, std, max, min; its log_std/ and ratio/ slots stay at the cleared 0. ro->rets_dev,
+ * ro->values_dev and ro->logp_old_dev are not read. Eager only: refuses a capturing stream. */
+int v4l_trainer_reinforce_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rstats_all_dev,
+                                      void* stream);
+/* The next REINFORCE update of the run opened by v4l_trainer_begin, by the rules of v4l_trainer_a2c_update_next: with use_graph
+ * the first update of a configuration runs eagerly, later ones are one hipGraph replay each. REINFORCE graphs have a key (the
+ * v4l_rollout, n and v4l_ppo_hyper bytes, the nets' generations, rstats_all_dev) and handles of their own; an update of one
+ * kind on a trainer drops the graphs of the other kinds. Same kernels, same arguments, same bits as the eager sequence. */
+int v4l_trainer_reinforce_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rstats_all_dev,
+                                      int use_graph, void* stream);
+/* `count` such updates behind one v4l_trainer_begin — the epoch is one pass over the samples (on_rl_algo.py:36-41); with
+ * use_graph, on a configuration that has run before, ONE hipGraph replay for all of them (captured by the first such call,
+ * re-captured when count changes). Otherwise update by update. */
+int v4l_trainer_reinforce_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rstats_all_dev,
+                                     int count, int use_graph, void* stream);
+/* REINFORCE graphs instantiated and hipGraphLaunch calls made by the two entries above since the trainer was created */
+int v4l_trainer_reinforce_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays);
+
 /* ---- data parallel: one process per GPU, every rank owns an env shard and its own rollout; gradients are
  * summed with ONE in-place RCCL all-reduce per optimiser step on the flat gradient buffer. The reference has no
  * counterpart (single process); the exchange sits where `vf_loss.backward()` / `policy_loss.backward()` end

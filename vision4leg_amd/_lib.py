@@ -23,6 +23,7 @@ V4L_MAX_ACT = 16   # widest action vector of a policy (include/v4l_hip.h)
 V4L_VMPO_STATS = 12   # floats per update in the V-MPO record (include/v4l_hip.h)
 V4L_VMPO_STATE = 7    # doubles of v4l_trainer_vmpo_state: eta, alpha, exp_avg x 2, exp_avg_sq x 2, step
 V4L_A2C_STATS = 16    # floats per update in the A2C record (include/v4l_hip.h)
+V4L_REINFORCE_STATS = 12   # floats per update in the REINFORCE record (include/v4l_hip.h)
 V4L_BUCKET_TAIL = 8   # scalars behind the gradients of an all-reduce bucket
 V4L_COMM_ID_BYTES = 128
 
@@ -64,6 +65,11 @@ VMPO_INFO_KEYS = (STAT_KEYS[:7] + VMPO_STAT_KEYS[:3] + STAT_KEYS[7:11] + VMPO_ST
 # the A2C record's first 12 slots = the keys A2C.update returns, in the reference's order (torchrl/algo/on_policy/a2c.py:89-105)
 A2C_INFO_KEYS = ["Training/policy_loss", "Training/vf_loss", "v_pred/mean", "v_pred/std", "v_pred/max", "v_pred/min",
                  "std/mean", "std/std", "std/max", "std/min", "ent", "log_prob"]
+
+# the REINFORCE record's first 10 slots = the keys Reinforce.update returns, in the reference's order
+# (torchrl/algo/on_policy/reinforce.py:43-74)
+REINFORCE_INFO_KEYS = ["advs/mean", "advs/std", "advs/max", "advs/min", "Training/policy_loss", "ent",
+                       "logprob/mean", "logprob/std", "logprob/max", "logprob/min"]
 
 
 class VMPOHyper(C.Structure):
@@ -175,6 +181,10 @@ _SIGS = {
   "v4l_trainer_a2c_update_next": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), _P, C.c_int, _P]),
   "v4l_trainer_a2c_update_run": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), _P, C.c_int, C.c_int, _P]),
   "v4l_trainer_a2c_graph_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+  "v4l_trainer_reinforce_actor_grads": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), _P, _P]),
+  "v4l_trainer_reinforce_update_next": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), _P, C.c_int, _P]),
+  "v4l_trainer_reinforce_update_run": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), _P, C.c_int, C.c_int, _P]),
+  "v4l_trainer_reinforce_graph_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
   "v4l_comm_available": (C.c_int, []),
   "v4l_trainer_comm_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
   "v4l_comm_unique_id": (C.c_int, [C.c_char_p]),

@@ -1497,6 +1497,100 @@ __global__ __launch_bounds__(1024) void a2c_loss_kernel(ActorArgs p, const UpdCt
     ast[AST_LOGP] = (float)lpm;
   }
 }
+
+// --------------------------------------------------------------------------------- REINFORCE (torchrl/algo/on_policy/reinforce.py)
+// V4L_REINFORCE_STATS floats per update, next to the PPO record: the 10 logger scalars of Reinforce.update in the reference's
+// order (reinforce.py:43-74); slots 10, 11 stay as the caller cleared them.
+enum { RST_ADV_MEAN = 0, RST_ADV_STD, RST_ADV_MAX, RST_ADV_MIN, RST_PI_LOSS, RST_ENT, RST_LP_MEAN, RST_LP_STD, RST_LP_MAX, RST_LP_MIN,
+       RST_SIZE = V4L_REINFORCE_STATS };
+static_assert(RST_LP_MIN < RST_SIZE, "the REINFORCE record holds the 10 keys");
+// Reinforce.update's policy loss (reinforce.py:52-61) and its gradient w.r.t. the policy mean [n][OUT_LD] and log sigma [A];
+// single block, the sibling of a2c_loss_kernel: the same rows, the same log sigma reduction with the entropy term and the clamp
+// gate, and on top of it logprob/std (Bessel), max, min (reinforce.py:69-72). No critic, so no std/* of A2C's record; advs/mean,
+// max and min are copied from the PPO record, where the opening launch left them, advs/std is formed from its M2 slot.
+//   policy_loss = mean_i(-logp_i an_i) - ent_coef ent        an: the advantage normalised with the minibatch statistics in p.st
+//   ent = sum_a (0.5 + 0.5 log(2 pi) + log sigma_a): the plain Normal's also for TanhNormal policies (distribution.py:79-80)
+// Fills ST_PI_LOSS and ST_LP_MEAN / STD / MAX / MIN of the PPO record (the closing Adam launch's non-finite count reads them); its
+// ST_LS_* and ST_RATIO_* stay at the cleared 0. A sibling, not a shared body: a2c_loss_kernel reduces two sums and no extrema,
+// and its instantiations stay the code they were.
+template <bool TANH, int CAP>
+__global__ __launch_bounds__(1024) void reinforce_loss_kernel(ActorArgs p, const UpdCtl* __restrict__ ctl, float* __restrict__ rst_all) {
+  __shared__ float sdl[16][CAP];
+  const int n = p.n, A = p.A;
+  const ActorDimsT<CAP> D = actor_dims<CAP>(p);
+  float dl[CAP];
+#pragma unroll
+  for (int a = 0; a < CAP; ++a) dl[a] = 0.f;
+  const float amean = p.st[ST_ADV_MEAN], astd = p.st[ST_ADV_STD];
+  double s_lp = 0.0, s_lp2 = 0.0, s_loss = 0.0;
+  float lp_mx = -INFINITY, lp_mn = INFINITY;
+  int sat = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int slot = p.rowidx ? p.rowidx[i] : i;
+    const float an = (p.adv[slot] - amean) / (astd + 1e-5f);
+    const float dlp = -p.inv_n * an;  // d(mean(-logp an)) / d(logp_i)
+    float mu[CAP], dmr[CAP];
+    actor_load_row(p.mean + (int64_t)i * OUT_LD, mu);
+    float lp = 0.f;
+#pragma unroll
+    for (int a = 0; a < CAP; ++a) {
+      dmr[a] = 0.f;
+      if (a < A) {
+        const float act = p.acts[(int64_t)slot * A + a];
+        const float x = TANH ? tanh_pre(act) : act;
+        const float corr = TANH ? tanh_corr(act) : 0.f;
+        const float d = x - mu[a];
+        const float var = D.sg[a] * D.sg[a];
+        lp += -(d * d) / (2.f * var) - D.lsg[a] - HALF_LOG_2PI - corr;
+        dmr[a] = grad_out(dlp * (d / var), p.gscale, sat);
+        dl[a] += dlp * (d * d / var - 1.f);
+      }
+    }
+    actor_store_dmean(p.dmean + (int64_t)i * OUT_LD, dmr, true);
+    s_loss += (double)(-lp * an);
+    s_lp += lp; s_lp2 += (double)lp * lp;
+    lp_mx = fmaxf(lp_mx, lp); lp_mn = fminf(lp_mn, lp);
+  }
+  const Red4 r = block_red4(s_lp, s_lp2, lp_mx, lp_mn);
+  const Red4 r2 = block_red4(s_loss, (double)sat, 0.f, 0.f);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int a = 0; a < CAP; ++a) {
+    const float v = wave_sum(dl[a]);
+    if (lane == 0) sdl[w][a] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < A) {
+    const int a = threadIdx.x;
+    const float raw = p.logstd[a];
+    float g = 0.f;
+    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) g += sdl[k][a];
+    g += -p.ent_coef * p.inv_n * (float)n;  // the entropy term, as in actor_loss_body
+    p.dlogstd[a] = (raw >= LOG_SIG_MIN && raw <= LOG_SIG_MAX) ? g : 0.f;  // the clamp of continuous_policy.py:486-492 passes no gradient outside
+  }
+  if (threadIdx.x == 0) {
+    float* st = p.st;
+    const double dn = (double)n;
+    const double lpm = r.s / dn;
+    const float loss = (float)(r2.s / dn - (double)p.ent_coef * D.ent);
+    const float lps = (float)sqrt(fmax(0.0, (r.s2 - dn * lpm * lpm) / (dn - 1.0)));  // (n >= 2: never one element)
+    st[ST_PI_LOSS] = loss;
+    st[ST_LP_MEAN] = (float)lpm;
+    st[ST_LP_STD] = lps;
+    st[ST_LP_MAX] = r.mx; st[ST_LP_MIN] = r.mn;
+    if (p.gscale != 1.f) st[ST_F16_SAT] += (float)r2.s2;
+    float* rst = rst_all + (int64_t)ctl->upd_index * RST_SIZE;
+    // advs/std: the reference takes it from the numpy batch before the upload (reinforce.py:43-46), so it is numpy's std — the
+    // population one, sqrt(M2 / n) — while the normalisation above uses torch's (Bessel) as reinforce.py:57 does
+    rst[RST_ADV_MEAN] = st[ST_ADV_MEAN]; rst[RST_ADV_STD] = (float)sqrt((double)st[ST_ADV_M2] / dn);
+    rst[RST_ADV_MAX] = st[ST_ADV_MAX]; rst[RST_ADV_MIN] = st[ST_ADV_MIN];
+    rst[RST_PI_LOSS] = loss;
+    rst[RST_ENT] = D.ent;
+    rst[RST_LP_MEAN] = (float)lpm;
+    rst[RST_LP_STD] = lps;
+    rst[RST_LP_MAX] = r.mx; rst[RST_LP_MIN] = r.mn;
+  }
+}
 #pragma clang fp contract(fast)
 
 // --------------------------------------------------------------------------------- weight packing

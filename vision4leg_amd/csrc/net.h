@@ -275,4 +275,12 @@ struct v4l_trainer {
   int aexec_run_count = 0;
   bool awarm = false;
   int64_t a2c_captures = 0, a2c_replays = 0;  // graphs instantiated / hipGraphLaunch calls (v4l_trainer_a2c_graph_counts)
+  // hipGraphs of a REINFORCE update / of a run of them: the same key type (GraphKey + the record array), a key and handles of
+  // their own (v4l_trainer_reinforce_update_next)
+  A2cGraphKey rkey = {};
+  hipGraphExec_t rexec = nullptr;
+  hipGraphExec_t rexec_run = nullptr;
+  int rexec_run_count = 0;
+  bool rwarm = false;
+  int64_t reinforce_captures = 0, reinforce_replays = 0;  // (v4l_trainer_reinforce_graph_counts)
 };

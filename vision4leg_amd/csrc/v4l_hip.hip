@@ -2664,6 +2664,15 @@ static int launch_vmpo_loss(hipStream_t s, const ActorArgs& aa, const VmpoArgs& 
   return 0;
 }
 
+// REINFORCE: the single-block loss launch (csrc/elem.h)
+template <int CAP>
+static int launch_reinforce_loss(hipStream_t s, const ActorArgs& aa, const UpdCtl* ctl, float* rst_all, dim3 blk) {
+  if (aa.tanh_action) V4L_KLAUNCH("reinforce_loss", 0, s, (reinforce_loss_kernel<true, CAP>), dim3(1), blk, 0, s, aa, ctl, rst_all);
+  else V4L_KLAUNCH("reinforce_loss", 0, s, (reinforce_loss_kernel<false, CAP>), dim3(1), blk, 0, s, aa, ctl, rst_all);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
+
 // A2C: the policy's single-block loss launch (csrc/elem.h)
 template <int CAP>
 static int launch_a2c_loss(hipStream_t s, const ActorArgs& aa, const UpdCtl* ctl, float* ast_all, dim3 blk) {
@@ -2698,7 +2707,9 @@ extern "C" {
 const char* v4l_last_error(void) { return v4l::last_error(); }
 // 113: v4l_net_cfg.has_logstd = V4L_LOGSTD_HEAD (GaussianContPolicy, continuous_policy.py:222-236: log sigma from the head's last layer, per row) —
 // actor_loss_sd_kernel, the per-row sampling epilogues of rollout_mlp_kernel / act_finish_sd_kernel, v4l_gauss_head_sd
-int v4l_version(void) { return 113; }  // 112: A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
+// 114: REINFORCE on every net kind the PPO update takes: v4l_trainer_reinforce_actor_grads / _update_next / _update_run / _graph_counts,
+// V4L_REINFORCE_STATS (reinforce_loss_kernel; the opening launch packs the policy)
+int v4l_version(void) { return 114; }  // 112: A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
 int v4l_abi_sizeof(int which) {
   return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) :
          which == 4 ? (int)sizeof(v4l_vmpo_hyper) : -1;  // (3 stays unassigned)
@@ -3400,10 +3411,17 @@ static void drop_a2c_graph(v4l_trainer* tr) {
   tr->aexec_run_count = 0;
   tr->awarm = false;
 }
+static void drop_reinforce_graph(v4l_trainer* tr) {
+  if (tr->rexec) { (void)hipGraphExecDestroy(tr->rexec); tr->rexec = nullptr; }
+  if (tr->rexec_run) { (void)hipGraphExecDestroy(tr->rexec_run); tr->rexec_run = nullptr; }
+  tr->rexec_run_count = 0;
+  tr->rwarm = false;
+}
 static void drop_graph(v4l_trainer* tr) {
   drop_ppo_graph(tr);
   drop_vmpo_graph(tr);
   drop_a2c_graph(tr);
+  drop_reinforce_graph(tr);
 }
 void v4l_trainer_destroy(v4l_trainer* tr) {
   if (tr) drop_graph(tr);
@@ -4005,6 +4023,7 @@ int v4l_trainer_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const
   hipStream_t s = (hipStream_t)stream;
   drop_vmpo_graph(tr);  // (a PPO update on a V-MPO trainer runs the policy's pass over n rows: other descriptor tables)
   drop_a2c_graph(tr);
+  drop_reinforce_graph(tr);
   if (!use_graph || g_prof || s == nullptr) return run_update(tr, ro, n, hp, stream);
   // the captured launch sequence is specific to (rollout pointers, n, hyper-parameters)
   GraphKey key;
@@ -4102,6 +4121,7 @@ int v4l_trainer_vmpo_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, 
   V4L_REQUIRE(!capturing(s), "v4l_trainer_vmpo_update_next: called under a caller's stream capture (use_graph = 1 captures itself)");
   drop_ppo_graph(tr);  // (the policy's pass runs over ceil(n / 2) rows here: other descriptor tables than a PPO update's)
   drop_a2c_graph(tr);
+  drop_reinforce_graph(tr);
   if (!use_graph || g_prof || s == nullptr) return run_vmpo_update(tr, ro, n, hp, vstats_all_dev, stream);
   VmpoGraphKey key;
   vmpo_graph_key(tr, ro, n, hp, vstats_all_dev, &key);
@@ -4242,80 +4262,211 @@ static int run_a2c_update(v4l_trainer* tr, const v4l_rollout* ro, int n, const v
   if ((rc = a2c_actor_stage(tr, ro, n, hp, astats_all_dev, stream))) return rc;
   return v4l_trainer_actor_step(tr, hp, stream);
 }
-static void a2c_graph_key(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, const float* astats_all_dev,
+// ---- the graphed driver of the learners whose captured update is keyed on GraphKey + one record array (A2C, REINFORCE). A
+// learner L names its entry points, checks the arguments (L::check), launches one update (L::run), owns its graph state in the
+// trainer (L::state) and drops the graphs of the other kinds (L::drop_others); the rules are v4l_trainer_update_next's.
+extern "C++" {  // (templates: this file's C ABI block is open here)
+struct RecGraphState {
+  A2cGraphKey* key; hipGraphExec_t* exec; hipGraphExec_t* exec_run; int* run_count; bool* warm; int64_t* captures; int64_t* replays;
+};
+static void rec_graph_key(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, const float* rec_all_dev,
                           A2cGraphKey* key) {
   memset(key, 0, sizeof(*key));
   key->base.ro = *ro; memcpy(&key->base.hp, hp, sizeof(*hp)); key->base.n = n;  // (bytewise: v4l_ppo_hyper ends in padding)
   key->base.gen[0] = tr->pf->gen; key->base.gen[1] = tr->vf->gen; key->base.gen[2] = tr->tpf->gen;
-  key->astats_all = astats_all_dev;
+  key->astats_all = rec_all_dev;
 }
-// Captures `count` A2C updates on s into *exec
-static int capture_a2c(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev, int count,
+// Captures `count` updates of learner L on s into *exec
+template <class L>
+static int rec_capture(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rec_all_dev, int count,
                        hipStream_t s, hipGraphExec_t* exec) {
-  V4L_TRACE("a2c update: %d update(s)", count);
+  V4L_TRACE("%s: %d update(s)", L::what, count);
   auto run = [&]() {
     int rb = 0;
-    for (int u = 0; u < count && !rb; ++u) rb = run_a2c_update(tr, ro, n, hp, astats_all_dev, (void*)s);
+    for (int u = 0; u < count && !rb; ++u) rb = L::run(tr, ro, n, hp, rec_all_dev, (void*)s);
     return rb;
   };
-  if (int rc = capture_graph(s, "a2c update", run, exec)) return rc;
-  ++tr->a2c_captures;
+  if (int rc = capture_graph(s, L::what, run, exec)) return rc;
+  ++*L::state(tr).captures;
   return 0;
 }
-int v4l_trainer_a2c_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,
-                                int use_graph, void* stream) {
-  int rc = check_a2c_args(tr, ro, n, hp, astats_all_dev);
+template <class L>
+static int rec_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rec_all_dev, int use_graph,
+                           void* stream) {
+  int rc = L::check(tr, ro, n, hp, rec_all_dev);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  V4L_REQUIRE(!capturing(s), "v4l_trainer_a2c_update_next: called under a caller's stream capture (use_graph = 1 captures itself)");
-  drop_ppo_graph(tr);
-  drop_vmpo_graph(tr);
-  if (!use_graph || g_prof || s == nullptr) return run_a2c_update(tr, ro, n, hp, astats_all_dev, stream);
+  V4L_REQUIRE(!capturing(s), "%s: called under a caller's stream capture (use_graph = 1 captures itself)", L::next_name);
+  L::drop_others(tr);
+  if (!use_graph || g_prof || s == nullptr) return L::run(tr, ro, n, hp, rec_all_dev, stream);
+  const RecGraphState g = L::state(tr);
   A2cGraphKey key;
-  a2c_graph_key(tr, ro, n, hp, astats_all_dev, &key);
-  if (memcmp(&key, &tr->akey, sizeof(key)) != 0) { drop_a2c_graph(tr); tr->akey = key; }
-  if (!tr->awarm) {  // first update of a configuration runs eagerly: it uploads the descriptor tables
-    tr->awarm = true;
-    return run_a2c_update(tr, ro, n, hp, astats_all_dev, stream);
+  rec_graph_key(tr, ro, n, hp, rec_all_dev, &key);
+  if (memcmp(&key, g.key, sizeof(key)) != 0) { L::drop(tr); *g.key = key; }
+  if (!*g.warm) {  // first update of a configuration runs eagerly: it uploads the descriptor tables
+    *g.warm = true;
+    return L::run(tr, ro, n, hp, rec_all_dev, stream);
   }
-  if (tr->aexec == nullptr && (rc = capture_a2c(tr, ro, n, hp, astats_all_dev, 1, s, &tr->aexec))) return rc;
-  V4L_HIP_CHECK(hipGraphLaunch(tr->aexec, s));
-  ++tr->a2c_replays;
+  if (*g.exec == nullptr && (rc = rec_capture<L>(tr, ro, n, hp, rec_all_dev, 1, s, g.exec))) return rc;
+  V4L_HIP_CHECK(hipGraphLaunch(*g.exec, s));
+  ++*g.replays;
   return 0;
 }
-int v4l_trainer_a2c_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,
-                               int count, int use_graph, void* stream) {
-  int rc = check_a2c_args(tr, ro, n, hp, astats_all_dev);
+template <class L>
+static int rec_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rec_all_dev, int count,
+                          int use_graph, void* stream) {
+  int rc = L::check(tr, ro, n, hp, rec_all_dev);
   if (rc) return rc;
-  V4L_REQUIRE(count >= 1, "v4l_trainer_a2c_update_run: count must be >= 1");
+  V4L_REQUIRE(count >= 1, "%s: count must be >= 1", L::run_name);
   hipStream_t s = (hipStream_t)stream;
-  V4L_REQUIRE(!capturing(s), "v4l_trainer_a2c_update_run: called under a caller's stream capture (use_graph = 1 captures itself)");
+  V4L_REQUIRE(!capturing(s), "%s: called under a caller's stream capture (use_graph = 1 captures itself)", L::run_name);
+  const RecGraphState g = L::state(tr);
   A2cGraphKey key;
-  a2c_graph_key(tr, ro, n, hp, astats_all_dev, &key);
-  const bool same = memcmp(&key, &tr->akey, sizeof(key)) == 0;
-  if (!use_graph || g_prof || s == nullptr || !same || !tr->awarm) {
+  rec_graph_key(tr, ro, n, hp, rec_all_dev, &key);
+  const bool same = memcmp(&key, g.key, sizeof(key)) == 0;
+  if (!use_graph || g_prof || s == nullptr || !same || !*g.warm) {
     // no graph, or a configuration this trainer has not run yet: update by update (the first one eagerly, then single-update
     // replays); the next call captures the whole run
     for (int u = 0; u < count; ++u)
-      if ((rc = v4l_trainer_a2c_update_next(tr, ro, n, hp, astats_all_dev, use_graph, stream))) return rc;
+      if ((rc = rec_update_next<L>(tr, ro, n, hp, rec_all_dev, use_graph, stream))) return rc;
     return 0;
   }
-  if (tr->aexec_run != nullptr && tr->aexec_run_count != count) {
-    (void)hipGraphExecDestroy(tr->aexec_run);
-    tr->aexec_run = nullptr;
+  if (*g.exec_run != nullptr && *g.run_count != count) {
+    (void)hipGraphExecDestroy(*g.exec_run);
+    *g.exec_run = nullptr;
   }
-  if (tr->aexec_run == nullptr) {
-    if ((rc = capture_a2c(tr, ro, n, hp, astats_all_dev, count, s, &tr->aexec_run))) return rc;
-    tr->aexec_run_count = count;
+  if (*g.exec_run == nullptr) {
+    if ((rc = rec_capture<L>(tr, ro, n, hp, rec_all_dev, count, s, g.exec_run))) return rc;
+    *g.run_count = count;
   }
-  V4L_HIP_CHECK(hipGraphLaunch(tr->aexec_run, s));
-  ++tr->a2c_replays;
+  V4L_HIP_CHECK(hipGraphLaunch(*g.exec_run, s));
+  ++*g.replays;
   return 0;
+}
+}  // extern "C++"
+struct A2cLearner {
+  static constexpr const char* what = "a2c update";
+  static constexpr const char* next_name = "v4l_trainer_a2c_update_next";
+  static constexpr const char* run_name = "v4l_trainer_a2c_update_run";
+  static int check(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, const float* rec) {
+    return check_a2c_args(tr, ro, n, hp, rec);
+  }
+  static int run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rec, void* stream) {
+    return run_a2c_update(tr, ro, n, hp, rec, stream);
+  }
+  static RecGraphState state(v4l_trainer* tr) {
+    return {&tr->akey, &tr->aexec, &tr->aexec_run, &tr->aexec_run_count, &tr->awarm, &tr->a2c_captures, &tr->a2c_replays};
+  }
+  static void drop(v4l_trainer* tr) { drop_a2c_graph(tr); }
+  static void drop_others(v4l_trainer* tr) { drop_ppo_graph(tr); drop_vmpo_graph(tr); drop_reinforce_graph(tr); }
+};
+int v4l_trainer_a2c_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,
+                                int use_graph, void* stream) {
+  return rec_update_next<A2cLearner>(tr, ro, n, hp, astats_all_dev, use_graph, stream);
+}
+int v4l_trainer_a2c_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* astats_all_dev,
+                               int count, int use_graph, void* stream) {
+  return rec_update_run<A2cLearner>(tr, ro, n, hp, astats_all_dev, count, use_graph, stream);
 }
 int v4l_trainer_a2c_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays) {
   V4L_REQUIRE(tr && captures && replays, "v4l_trainer_a2c_graph_counts: null argument");
   *captures = tr->a2c_captures;
   *replays = tr->a2c_replays;
+  return 0;
+}
+
+// ---- REINFORCE (torchrl/algo/on_policy/reinforce.py:34-76) on every net kind: the opening launch on the POLICY's packs, its
+// forward, one loss launch of its own, its backward, clip + Adam. No critic launch of any kind.
+static int check_reinforce_args(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, const float* rstats_all_dev) {
+  int rc = check_update_args(tr, ro, n, hp);
+  if (rc) return rc;
+  V4L_REQUIRE(rstats_all_dev != nullptr, "v4l_trainer_reinforce: the REINFORCE record array is missing");
+  V4L_REQUIRE(!tr->pf->sd(), "v4l_trainer_reinforce: a V4L_LOGSTD_HEAD policy (GaussianContPolicy) runs under the PPO update only: the "
+              "REINFORCE loss kernel takes one log sigma per action column");
+  V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_reinforce: REINFORCE runs in a single process");
+  V4L_REQUIRE(tr->skip_all == nullptr,
+              "v4l_trainer_reinforce: no skipping of non-finite steps (v4l_trainer_begin_guarded) in a REINFORCE run");
+  return 0;
+}
+// reinforce.py:52-63 (pf.update(obs, acts), policy_loss, policy_loss.backward())
+static int reinforce_actor_stage(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rstats_all_dev,
+                                 void* stream) {
+  int rc;
+  hipStream_t s = (hipStream_t)stream;
+  v4l_net* pf = tr->pf;
+  const int* rowidx = tr->rowidx_cur;
+  g_op = "ctl";
+  // v4l_trainer_critic_grads' opening launch with the policy's packs in the critic's place: rows, cleared record, Adam step
+  // sizes and advantage statistics (block 0) next to the weight copies the previous policy step outdated (the other blocks)
+  if ((rc = by_compute(pf->cfg.compute, [&](auto tag) -> int {
+        typedef typename decltype(tag)::type T;
+        V4L_KLAUNCH("begin_pack", 0, s, begin_pack_kernel<T>, dim3((unsigned)pf->pack_blocks + 1), dim3(256), 0, s, tr->ctl, tr->rowidx_all, n,
+                    tr->rowidx_cur, tr->stats_cur, ro->advs_dev, pf->d_packs, (int)pf->packs.size(), (T*)pf->packed);
+        V4L_LAUNCH_CHECK();
+        return 0;
+      })))
+    return rc;
+  const Layout Lp = pf->layout(n);
+  { PhaseScope ps("pf.fwd");
+  if ((rc = v4l_net_forward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, 1, stream))) return rc; }
+  g_op = "loss";
+  {
+    ActorArgs aa;
+    memset(&aa, 0, sizeof(aa));
+    aa.mean = tr->ws + Lp.out; aa.logstd = pf->p[pf->logstd];
+    aa.acts = ro->acts_dev; aa.adv = ro->advs_dev; aa.rowidx = rowidx;
+    aa.n = n; aa.A = pf->cfg.out_dim; aa.inv_n = 1.f / (float)n; aa.ent_coef = hp->entropy_coeff;
+    aa.dmean = tr->ws + Lp.dout; aa.dlogstd = tr->g_pf + pf->params[pf->logstd].goff; aa.st = tr->stats_cur;
+    aa.tanh_action = pf->cfg.tanh_action;
+    aa.gscale = v4l_net_grad_scale(pf, n);
+    const dim3 blk(n >= 512 ? 1024 : 256);
+    rc = act_cap(aa.A) != ACT_CAP_NARROW ? launch_reinforce_loss<V4L_MAX_ACT>(s, aa, tr->ctl, rstats_all_dev, blk)
+                                         : launch_reinforce_loss<ACT_CAP_NARROW>(s, aa, tr->ctl, rstats_all_dev, blk);
+    if (rc) return rc;
+  }
+  PhaseScope ps("pf.bwd");
+  return v4l_net_backward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, tr->g_pf, stream);
+}
+int v4l_trainer_reinforce_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rstats_all_dev,
+                                      void* stream) {
+  int rc = check_reinforce_args(tr, ro, n, hp, rstats_all_dev);
+  if (rc) return rc;
+  V4L_REQUIRE(!capturing((hipStream_t)stream), "v4l_trainer_reinforce_actor_grads: called under a caller's stream capture");
+  return reinforce_actor_stage(tr, ro, n, hp, rstats_all_dev, stream);
+}
+static int run_reinforce_update(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rstats_all_dev,
+                                void* stream) {
+  if (int rc = reinforce_actor_stage(tr, ro, n, hp, rstats_all_dev, stream)) return rc;
+  return v4l_trainer_actor_step(tr, hp, stream);
+}
+struct ReinforceLearner {
+  static constexpr const char* what = "reinforce update";
+  static constexpr const char* next_name = "v4l_trainer_reinforce_update_next";
+  static constexpr const char* run_name = "v4l_trainer_reinforce_update_run";
+  static int check(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, const float* rec) {
+    return check_reinforce_args(tr, ro, n, hp, rec);
+  }
+  static int run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rec, void* stream) {
+    return run_reinforce_update(tr, ro, n, hp, rec, stream);
+  }
+  static RecGraphState state(v4l_trainer* tr) {
+    return {&tr->rkey, &tr->rexec, &tr->rexec_run, &tr->rexec_run_count, &tr->rwarm, &tr->reinforce_captures, &tr->reinforce_replays};
+  }
+  static void drop(v4l_trainer* tr) { drop_reinforce_graph(tr); }
+  static void drop_others(v4l_trainer* tr) { drop_ppo_graph(tr); drop_vmpo_graph(tr); drop_a2c_graph(tr); }
+};
+int v4l_trainer_reinforce_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rstats_all_dev,
+                                      int use_graph, void* stream) {
+  return rec_update_next<ReinforceLearner>(tr, ro, n, hp, rstats_all_dev, use_graph, stream);
+}
+int v4l_trainer_reinforce_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float* rstats_all_dev,
+                                     int count, int use_graph, void* stream) {
+  return rec_update_run<ReinforceLearner>(tr, ro, n, hp, rstats_all_dev, count, use_graph, stream);
+}
+int v4l_trainer_reinforce_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays) {
+  V4L_REQUIRE(tr && captures && replays, "v4l_trainer_reinforce_graph_counts: null argument");
+  *captures = tr->reinforce_captures;
+  *replays = tr->reinforce_replays;
   return 0;
 }
 

@@ -534,18 +534,19 @@ class HipTrainer:
     self._steps_on_device = False
     self.step = int(updates) if updates is not None else max(self._adam_steps)
 
-  def _count(self, updates):
+  def _count(self, updates, critic=True):
+    """critic=False: updates that step the policy's optimiser alone (REINFORCE) — the critic's Adam count stays where it is."""
     self.step += updates
     if self._guarded:
       self._steps_on_device = True
     else:
-      self._adam_steps = (self._adam_steps[0] + updates, self._adam_steps[1] + updates)
+      self._adam_steps = (self._adam_steps[0] + updates, self._adam_steps[1] + (updates if critic else 0))
 
-  def _call_update(self, entry, ro, n, tail, updates):
+  def _call_update(self, entry, ro, n, tail, updates, critic=True):
     """One library call that runs `updates` whole updates of the open run: entry(tr, ro, n, hp, *tail, stream)."""
     self._pre(n)
     check(getattr(self.L, entry)(self.h, C.byref(ro), n, C.byref(self.hp), *tail, _stream()), entry)
-    self._count(updates)
+    self._count(updates, critic)
     self._after_steps()
 
   def update_next(self, ro, n, graph=True):
@@ -684,6 +685,31 @@ class HipTrainer:
   def a2c_graph_counts(self):
     """-> (A2C graphs instantiated, A2C graph replays launched) since this trainer was created."""
     return self._graph_counts("v4l_trainer_a2c_graph_counts")
+
+  # ---- REINFORCE (torchrl/algo/on_policy/reinforce.py:34-76) on every net kind: the policy's half of an update and nothing else;
+  # the critic's Adam count never advances. rstats_all: [U][V4L_REINFORCE_STATS] float32 device tensor of the open run's
+  # REINFORCE records (zeroed by the caller)
+  def reinforce_actor_grads(self, ro, n, rstats_all):
+    """reinforce.py:52-63 up to policy_loss.backward() (v4l_trainer_reinforce_actor_grads): the opening launch through the
+    policy's backward; actor_step() would follow (it counts a critic step too: tests that look at gradients do not call it)."""
+    self._pre(n)
+    check(self.L.v4l_trainer_reinforce_actor_grads(self.h, C.byref(ro), n, C.byref(self.hp), _ptr(rstats_all), _stream()),
+          "v4l_trainer_reinforce_actor_grads")
+
+  def reinforce_update_next(self, ro, n, rstats_all, graph=False):
+    """The next REINFORCE minibatch update of the run begin() opened (v4l_trainer_reinforce_update_next). graph=True: one hipGraph
+    replay once the configuration has run; graph=False: eager launches."""
+    self._call_update("v4l_trainer_reinforce_update_next", ro, n, (_ptr(rstats_all), int(graph)), 1, critic=False)
+
+  def reinforce_update_run(self, ro, n, count, rstats_all, graph=True):
+    """The next `count` REINFORCE updates behind one begin(): with graph=True ONE hipGraph replay for all of them
+    (v4l_trainer_reinforce_update_run). Keep the row-index, record and rstats_all tensors at one address from run to run: the
+    graph is keyed on them."""
+    self._call_update("v4l_trainer_reinforce_update_run", ro, n, (_ptr(rstats_all), int(count), int(graph)), int(count), critic=False)
+
+  def reinforce_graph_counts(self):
+    """-> (REINFORCE graphs instantiated, REINFORCE graph replays launched) since this trainer was created."""
+    return self._graph_counts("v4l_trainer_reinforce_graph_counts")
 
 
 def vmpo_select(adv, rowidx, n):

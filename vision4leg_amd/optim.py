@@ -49,7 +49,10 @@ def resolve(optimizer_class=None, optimizer_kwargs=None, lr=3e-4, eps=1e-5):
         # (before the call: SGD, for one, takes no eps and would die on the reference's own call with a TypeError)
         raise NotImplementedError("vision4leg_amd: PPO runs Adam or AdamW on the HIP engine; optimizer_class is %s" % name)
     try:
-        opt = given([torch.nn.Parameter(torch.zeros(1))], lr=lr, eps=eps, **kwargs)
+        # eps=None: the reference's Reinforce call, `optimizer_class(params, lr=...)` (reinforce.py:26-29): torch's (or a
+        # partial's) own eps
+        call = {"lr": lr} if eps is None else {"lr": lr, "eps": eps}
+        opt = given([torch.nn.Parameter(torch.zeros(1))], **call, **kwargs)
     except TypeError as e:
         raise ValueError("vision4leg_amd: optimizer_class %s cannot be built as the reference builds it, "
                          "optimizer_class(params, lr=..., eps=1e-5): %s" % (name, e)) from None

@@ -10,6 +10,7 @@ stays the reference's, so `starter/ppo_*.py` runs unchanged:
     overlay.install(fast_path=True)   # + fused rollout step, HBM-resident replay buffer, pinned observation upload
     overlay.install(vmpo=True)        # + `torchrl.algo.VMPO` on the HIP engine (opt-in: the default leaves it the reference's)
     overlay.install(a2c=True)         # + `torchrl.algo.A2C` on the HIP engine, state-MLP nets only (opt-in, like vmpo)
+    overlay.install(reinforce=True)   # + `torchrl.algo.Reinforce` on the HIP engine, `networks.ZeroNet` -> this package's (opt-in)
     overlay.install(state_std=True)   # + `torchrl.policies.GaussianContPolicy` (log-std from the head) on the HIP engine (opt-in)
 
 Rebinding is by name on every already-imported `torchrl.<pkg>` module that defines the name (the package and the
@@ -50,6 +51,16 @@ A2C_NAMES = {
     "algo": ["A2C"],
 }
 
+# reinforce=True: the critic-free learner (`from torchrl.algo import Reinforce`). The reference's Reinforce imports ZeroNet for
+# its vacant critic; a starter that hands `networks.ZeroNet()` to the fast-path collector gets this package's class, which the
+# collector and algo.Reinforce turn into networks.zero_critic(pf) (rebound silently: the report names the learner only)
+REINFORCE_NAMES = {
+    "algo": ["Reinforce"],
+}
+REINFORCE_SILENT = {
+    "networks": ["ZeroNet"],
+}
+
 # state_std=True: the Gaussian policy with a state-dependent log-std head (continuous_policy.py:222-236), state-MLP nets under PPO
 STATE_STD_NAMES = {
     "policies": ["GaussianContPolicy"],
@@ -72,10 +83,12 @@ def _rebind(ref_pkg_name, name, obj, always_on_package=False):
     return hits
 
 
-def install(fast_path=False, reference_package="torchrl", vmpo=False, a2c=False, state_std=False):
+def install(fast_path=False, reference_package="torchrl", vmpo=False, a2c=False, state_std=False, reinforce=False):
     """Rebind the hot-path classes on the reference's `torchrl`. Returns {"pkg.name": [modules patched]}.
     vmpo=True also rebinds `torchrl.algo.VMPO` (vision4leg_amd.torchrl.algo.VMPO); without it VMPO stays the reference's.
     a2c=True also rebinds `torchrl.algo.A2C` (and nothing else); without it A2C stays the reference's.
+    reinforce=True also rebinds `torchrl.algo.Reinforce` and `torchrl.networks.ZeroNet` (the report gains "algo.Reinforce" only);
+    without it both stay the reference's.
     state_std=True also rebinds `torchrl.policies.GaussianContPolicy` (and nothing else); without it that class stays the reference's."""
     ref = importlib.import_module(reference_package)
     if getattr(ref, "__v4l_shell__", False):
@@ -102,7 +115,14 @@ def install(fast_path=False, reference_package="torchrl", vmpo=False, a2c=False,
             shell = importlib.import_module("vision4leg_amd.torchrl." + pkg)
             for name, shell_name in names.items():
                 report["%s.%s" % (pkg, name)] = _rebind(ref_name, name, getattr(shell, shell_name))
-    for wanted, table in ((vmpo, VMPO_NAMES), (a2c, A2C_NAMES), (state_std, STATE_STD_NAMES)):
+    if reinforce:
+        for pkg, names in REINFORCE_SILENT.items():
+            ref_name = "%s.%s" % (reference_package, pkg)
+            shell = importlib.import_module("vision4leg_amd.torchrl." + pkg)
+            for name in names:
+                if not _rebind(ref_name, name, getattr(shell, name)):
+                    raise RuntimeError("vision4leg_amd.overlay: the reference has no %s.%s to replace" % (ref_name, name))
+    for wanted, table in ((vmpo, VMPO_NAMES), (a2c, A2C_NAMES), (state_std, STATE_STD_NAMES), (reinforce, REINFORCE_NAMES)):
         if not wanted:
             continue
         for pkg, names in table.items():

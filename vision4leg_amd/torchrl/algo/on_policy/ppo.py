@@ -187,6 +187,8 @@ def _check_update_records(stats, flags, guarded, label=lambda u: "minibatch upda
 
 
 class PPO:
+    _call_eps = 1e-5  # the eps the reference's constructor hands optimizer_class (a2c.py:30-40); None: it hands none (reinforce.py:26-29)
+
     def __init__(self, pf, vf, plr=3e-4, vlr=3e-4, optimizer_class=None, entropy_coeff=0.001, clip_para=0.2,
                  opt_epochs=10, clipped_value_loss=False, shuffle=True, tau=None, gae=True, env=None,
                  replay_buffer=None, collector=None, logger=None, grad_clip=None, discount=0.99, num_epochs=3000,
@@ -194,7 +196,7 @@ class PPO:
                  save_train_state=False, resume=None, optimizer_kwargs=None, **kwargs):
         # torch.optim.Adam / AdamW, a functools.partial of either, or "Adam" / "AdamW" + optimizer_kwargs (JSON configs): resolved
         # the way the reference would build it, `optimizer_class(params, lr=..., eps=1e-5)` (a2c.py:30-40); anything else raises
-        opt = hip_optim.resolve(optimizer_class, optimizer_kwargs, lr=plr)
+        opt = hip_optim.resolve(optimizer_class, optimizer_kwargs, lr=plr, eps=self._call_eps)
         if getattr(pf, "logstd_head", False):  # policies.GaussianContPolicy: before anything touches a device
             forced = (os.environ.get("V4L_FORCE_DP_PHASES", "0") != "0" and torch.distributed.is_available()
                       and torch.distributed.is_initialized())

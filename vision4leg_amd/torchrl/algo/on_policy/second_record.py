@@ -1,5 +1,5 @@
-"""The shell of the learners whose update writes a second statistics record next to PPO's (VMPO, A2C): what they refuse, and a
-run of U updates on the trainer's stream whose two record arrays come back in one device-to-host copy. All updates of an epoch
+"""The shell of the learners whose update writes a second statistics record next to PPO's (VMPO, A2C, Reinforce): what they
+refuse, and a run of U updates on the trainer's stream whose two record arrays come back in one device-to-host copy. All updates of an epoch
 are ONE hipGraph replay, like PPO's (V4L_EPOCH_GRAPH=0: one replay per update; V4L_GRAPH=0: eager launches; update(batch): the
 single-update replay). Construction, the collector / buffer wiring, train(), snapshot and process_epoch_samples are PPO's.
 
@@ -10,6 +10,7 @@ A subclass declares:
   _syncs_target   trainer.sync_target() at the start of an epoch
   _run_entry, _next_entry   the HipTrainer methods that run U updates / the next update
   _info(row, second_row)    the logger's info dict of one update from the two records
+and may override _lr_vf() (the critic's learning rate handed to the opening launch: Reinforce keeps no public vf_optimizer).
 """
 import os
 
@@ -82,6 +83,10 @@ class _SecondRecordPPO(PPO):
             self._rows_buf.copy_(rowidx)
         return self._rows_buf, self._both_buf, self._first_buf, self._second_buf
 
+    def _lr_vf(self):
+        """The critic's learning rate of the run being opened (a learner that keeps no public vf_optimizer overrides this)."""
+        return self.vf_optimizer.lr
+
     def _run(self, ro, rowidx, n, U, what):
         """U updates on rows rowidx[u] (None: rows 0 .. n-1) on the trainer's stream, then ONE device-to-host copy of both record
         arrays and the host's checks. -> list of U info dicts. The whole run is ONE hipGraph replay (one replay per update with
@@ -92,7 +97,7 @@ class _SecondRecordPPO(PPO):
         tr.stream.wait_stream(cur)
         with torch.cuda.stream(tr.stream):
             tr._pre(n)
-            tr.begin(rows, stats, self.pf_optimizer.lr, self.vf_optimizer.lr)
+            tr.begin(rows, stats, self.pf_optimizer.lr, self._lr_vf())
             self.training_update_num += U
             if self.use_graph and os.environ.get("V4L_EPOCH_GRAPH", "1") != "0":
                 getattr(tr, self._run_entry)(ro, n, U, second, graph=True)

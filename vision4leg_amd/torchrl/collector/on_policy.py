@@ -21,6 +21,7 @@ import os
 import numpy as np
 import torch
 
+from .. import networks
 from ..replay_buffers import DeviceOnPolicyReplayBuffer
 
 
@@ -48,6 +49,8 @@ _NO_GUARD = _NoGuard()
 class VecOnPolicyCollector:
     def __init__(self, vf, discount=0.99, *, env, eval_env, pf, replay_buffer, epoch_frames, train_render=False,
                  eval_episodes=1, eval_render=False, device="cpu", max_episode_frames=999):
+        if isinstance(vf, networks.ZeroNet):  # the reference's vacant critic (algo.Reinforce): a zero critic on pf's trunk
+            vf = networks.zero_critic(pf)
         self.vf, self.pf = vf, pf
         self.discount = discount
         self.replay_buffer = replay_buffer

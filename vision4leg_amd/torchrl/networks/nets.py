@@ -371,3 +371,63 @@ class Transformer(_HipNetMixin, nn.Module):
         c.pytorch_encoder = int(bool(self.use_pytorch_encoder))  # nn.TransformerEncoder + final norm (nets.py:955-963)
         c.has_logstd = int(hasattr(self, "logstd"))
         return c
+
+
+class ZeroNet(nn.Module):
+    """The reference's vacant value network (nets.py:11-13; `Reinforce.vf`): no parameters, `forward` returns torch.zeros(1).
+    The engine's trainer, rollout step and return estimate take a critic net, so algo.Reinforce and VecOnPolicyCollector replace
+    an instance of this class with `zero_critic(pf)`."""
+
+    def forward(self, x):
+        return torch.zeros(1)
+
+
+def _trunk(net):
+    return net.base if isinstance(net, Net) else getattr(net, "encoder", None)
+
+
+def zero_critic(pf):
+    """A value net of pf's network class and geometry (output_shape=1) whose output is exactly 0: what ZeroNet gives the reference,
+    in the shape every route of the engine takes. Its trunk module IS pf's (`vf.base = pf.base` for Net, one `encoder` object
+    for the four vision classes, as the starters wire vf); the head's hidden layers (and a Transformer's layers) are its own, the
+    last Linear's weight and bias are exactly zero (0 * h + 0 = 0.0 in every compute mode), and none of its own parameters
+    requires grad. Built without drawing from torch's generator — constructing ZeroNet() draws nothing either."""
+    head = dict(output_shape=1, append_hidden_shapes=list(pf.append_hidden_shapes), activation_func=pf.activation_func,
+                add_ln=pf.add_ln)
+    with torch.random.fork_rng(devices=[]):
+        if isinstance(pf, Net):
+            vf = Net(base_type=lambda **kw: pf.base, **head)
+        elif isinstance(pf, ImpalaEncoderProjNet):
+            vf = ImpalaEncoderProjNet(encoder=pf.encoder, state_input_shape=pf.state_input_shape,
+                                      visual_input_shape=pf.visual_input_shape, detach=pf.detach, **head)
+        elif isinstance(pf, NatureEncoderProjNet):
+            vf = NatureEncoderProjNet(encoder=pf.encoder, visual_input_shape=pf.visual_input_shape, detach=pf.detach, **head)
+        elif isinstance(pf, (LocoTransformer, Transformer)):
+            kw = dict(encoder=pf.encoder, visual_input_shape=pf.visual_input_shape, transformer_params=list(pf.transformer_params),
+                      detach=pf.detach, state_detach=pf.state_detach, max_pool=pf.max_pool, token_norm=pf.token_norm,
+                      use_pytorch_encoder=pf.use_pytorch_encoder, **head)
+            if isinstance(pf, LocoTransformer):
+                vf = LocoTransformer(state_input_shape=pf.state_input_shape, **kw)
+            else:
+                vf = Transformer(**kw)
+        else:
+            raise NotImplementedError("vision4leg_amd: zero_critic: %s is not one of this package's network classes"
+                                      % type(pf).__name__)
+    shared = {id(p) for p in pf.parameters()}
+    last = (vf.seq_append_fcs if hasattr(vf, "seq_append_fcs") else vf.visual_seq_append_fcs)[-1]
+    with torch.no_grad():
+        last.weight.zero_()
+        last.bias.zero_()
+    for p in vf.parameters():
+        if id(p) not in shared:
+            p.requires_grad_(False)
+    vf._zero_critic = True
+    first = next(pf.parameters(), None)
+    if first is not None:
+        vf.to(first.device)
+    return vf
+
+
+def is_zero_critic(vf, pf):
+    """True for a net zero_critic made on THIS pf's trunk."""
+    return bool(getattr(vf, "_zero_critic", False)) and _trunk(vf) is not None and _trunk(vf) is _trunk(pf)
