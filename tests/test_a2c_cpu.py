@@ -63,6 +63,25 @@ def test_seed_rule(name):
     assert worst <= ac.ORACLE_F32_ERR_MAX, worst
 
 
+def test_loss_rows_wide_block_oracle():
+    """What tests/test_gpu_a2c.py::test_loss_rows[a2c_mlp_odd@513] compares with, alone: the restatement at 513 rows with a log
+    sigma beyond either end of the clamp is finite everywhere, and its d(loss)/d(logstd) is exactly 0 at those two columns and
+    at no other."""
+    import vision4leg_amd.torchrl.networks as networks
+    import vision4leg_amd.torchrl.policies as policies
+    case = util.loss_rows_case(ac.A2C_CASES, "a2c_mlp_odd@513")
+    assert case["B"] == 513 and case["A"] == 12 and ac.A2C_CASES["a2c_mlp_odd"]["B"] == 23
+    assert util.loss_rows_both_ends("a2c_mlp_odd@513", "f32", False) and not util.loss_rows_both_ends("a2c_mlp_odd", "f32", False)
+    pf, vf = ac.seeded_nets(networks, policies, case)
+    logstd = util.loss_rows_logstd(case["A"], False, both_ends=True)
+    assert logstd[0] < -5.0 and logstd[-1] > 2.0 and (logstd[1:-1] > -5.0).all() and (logstd[1:-1] < 2.0).all()
+    util.spread_policy_head(pf, logstd)
+    dout, dls, dval, info = ac.oracle_of(pf.state_dict(), vf.state_dict(), case).loss_grads(*ac.batch_tensors(case, 0))
+    assert dout.shape == (513, 12) and torch.isfinite(dout).all() and torch.isfinite(dls).all() and torch.isfinite(dval).all()
+    assert np.isfinite(list(info.values())).all()
+    assert dls[0].item() == 0.0 and dls[-1].item() == 0.0 and (dls[1:-1] != 0).all()
+
+
 def test_case_nets_share_nothing_and_the_starters_pair_does():
     import vision4leg_amd.torchrl.networks as networks
     import vision4leg_amd.torchrl.policies as policies

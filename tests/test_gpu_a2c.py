@@ -64,24 +64,25 @@ def test_surface(device):
 
 # ------------------------------------------------------------------------------------------ one loss evaluation
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("name", ["a2c_mlp_odd", "a2c_mlp_tanh"])
+@pytest.mark.parametrize("name", ["a2c_mlp_odd", "a2c_mlp_tanh", "a2c_mlp_odd@513"])
 def test_loss_rows(name, mode, device):
     """a2c_critic_loss_kernel and a2c_loss_kernel through the trainer's eager phases, nothing stepped: d(vf_loss)/d(value) rows,
     d(policy_loss)/d(mean) rows, d/d(logstd) and the 12 statistics against autograd on the restatement. The policy gets distinct
     log sigmas (one beyond the clamp for the Normal policy: its gradient is gated to 0) and means O(1) first.
     Gradients: f32 par.TOL; 16-bit modes: the rows are linear in the head output, whose distance to the fp32 value is capped by
-    par.REF_DIST. Statistics: test_two_updates' info bounds."""
+    par.REF_DIST. Statistics: test_two_updates' info bounds.
+    "@513" (util.loss_rows_case): the capacity-16 kernels in their 1024-thread block; in f32 with a log sigma below LOG_SIG_MIN
+    too (util.loss_rows_both_ends): both ends of the gate exactly 0, and the columns beside that one held to the bound on their
+    own (its rows are 1 / sigma^2 = 2.2e4 times theirs and would carry the norm alone)."""
     from vision4leg_amd import _lib
     from vision4leg_amd.engine import HipTrainer
-    case = A2C_CASES[name]
+    case = util.loss_rows_case(A2C_CASES, name)
     A, n = case["A"], case["B"]
     tanh = case["kind"].endswith("_tanh")
     agent, pf, vf = _agent(case, mode, device)
     tr = agent.trainer
-    logstd = np.linspace(-1.0, 0.0 if tanh else 0.5, A).astype(np.float32)
-    if not tanh:
-        logstd[-1] = 2.5  # beyond LOG_SIG_MAX: sigma = e^2, no gradient
-    util.spread_policy_head(pf, logstd)
+    both_ends = util.loss_rows_both_ends(name, mode, tanh)
+    util.spread_policy_head(pf, util.loss_rows_logstd(A, tanh, both_ends))  # (the last one beyond LOG_SIG_MAX: sigma = e^2, no gradient)
     oracle = _oracle(pf, vf, case, mode)
     dout, dls, dval, oinfo = oracle.loss_grads(*ac.batch_tensors(case, 0))
     b = ac.host_batch(case, 0)
@@ -118,6 +119,9 @@ def test_loss_rows(name, mode, device):
     assert e_rows < tol and e_ls < tol and e_val < tol, (e_rows, e_ls, e_val)
     if not tanh:
         assert got_ls[-1].item() == 0.0 and dls[-1].item() == 0.0
+    if both_ends:
+        assert got_ls[0].item() == 0.0 and dls[0].item() == 0.0
+        assert util.rel_err(rows[:, 1:A], dout[:, 1:]) < tol
     assert (rec[len(INFO_KEYS):] == 0).all()
     for j, k in enumerate(INFO_KEYS):
         print("   %-22s % .6f % .6f" % (k, rec[j], oinfo[k]))

@@ -74,25 +74,26 @@ def test_surface(device):
 
 # ------------------------------------------------------------------------------------------ one loss evaluation
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("name", ["rf_mlp_odd", "rf_mlp_tanh"])
+@pytest.mark.parametrize("name", ["rf_mlp_odd", "rf_mlp_tanh", "rf_mlp_odd@513"])
 def test_loss_rows(name, mode, device):
     """reinforce_loss_kernel through the trainer's eager entry, nothing stepped: d(policy_loss)/d(mean) rows, d/d(logstd) and the
     10 statistics against the float64 loss stage (reinforce_cases.loss_stage64) on the head rows the forward left in the
     workspace. The policy gets distinct log sigmas (one beyond the clamp for the Normal policy: its gradient is gated to 0) and
     means O(1) first; the head rows are also held to the restatement's forward (par.TOL / par.REF_DIST), so the stage is fed what
     the reference's would be. Gradients: par.TOL["f32"] in f32, par.REF_DIST in the 16-bit modes. Statistics: test_two_updates'
-    info bounds."""
+    info bounds.
+    "@513" (util.loss_rows_case): the capacity-16 kernel in its 1024-thread block; in f32 with a log sigma below LOG_SIG_MIN
+    too (util.loss_rows_both_ends): both ends of the gate exactly 0, and the columns beside that one held to the bound on their
+    own (its rows are 1 / sigma^2 = 2.2e4 times theirs and would carry the norm alone)."""
     from vision4leg_amd import _lib
     from vision4leg_amd.engine import HipTrainer
-    case = REINFORCE_CASES[name]
+    case = util.loss_rows_case(REINFORCE_CASES, name)
     A, n = case["A"], case["B"]
     tanh = case["kind"].endswith("_tanh")
     agent, pf = _agent(case, mode, device)
     tr = agent.trainer
-    logstd = np.linspace(-1.0, 0.0 if tanh else 0.5, A).astype(np.float32)
-    if not tanh:
-        logstd[-1] = 2.5  # beyond LOG_SIG_MAX: sigma = e^2, no gradient
-    util.spread_policy_head(pf, logstd)
+    both_ends = util.loss_rows_both_ends(name, mode, tanh)
+    util.spread_policy_head(pf, util.loss_rows_logstd(A, tanh, both_ends))  # (the last one beyond LOG_SIG_MAX: sigma = e^2, no gradient)
     oracle = rc.oracle_of(pf.state_dict(), case, "f32")
     want_rows = oracle.fwd({k: v for k, v in oracle.pf.items() if k != "logstd"}, rc.batch_tensors(case, 0)[0], case["S"], "f32")
     b = rc.host_batch(case, 0)
@@ -132,6 +133,9 @@ def test_loss_rows(name, mode, device):
     assert e_rows < tol and e_ls < tol, (e_rows, e_ls)
     if not tanh:
         assert got_ls[-1].item() == 0.0 and dls[-1].item() == 0.0
+    if both_ends:
+        assert got_ls[0].item() == 0.0 and dls[0].item() == 0.0
+        assert util.rel_err(rows[:, 1:A], dout[:, 1:]) < tol
     assert len(rec) == 12 and (rec[len(INFO_KEYS):] == 0).all()
     for j, k in enumerate(INFO_KEYS):
         print("   %-22s % .6f % .6f" % (k, rec[j], oinfo[k]))

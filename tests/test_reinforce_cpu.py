@@ -64,6 +64,26 @@ def test_seed_rule(name):
     assert rc.SEED_LOG[name][0] == case["seed"]
 
 
+def test_loss_rows_wide_block_oracle():
+    """What tests/test_gpu_reinforce.py::test_loss_rows[rf_mlp_odd@513] compares with, alone: the float64 loss stage on the
+    restatement's head rows at 513 rows, with a log sigma beyond either end of the clamp, is finite everywhere, and its
+    d(loss)/d(logstd) is exactly 0 at those two columns and at no other."""
+    import vision4leg_amd.torchrl.networks as networks
+    import vision4leg_amd.torchrl.policies as policies
+    case = util.loss_rows_case(rc.REINFORCE_CASES, "rf_mlp_odd@513")
+    assert case["B"] == 513 and case["A"] == 12 and rc.REINFORCE_CASES["rf_mlp_odd"]["B"] == 23
+    pf = rc.seeded_policy(networks, policies, case)
+    util.spread_policy_head(pf, util.loss_rows_logstd(case["A"], False, both_ends=True))
+    oracle = rc.oracle_of(pf.state_dict(), case)
+    head = oracle.fwd({k: v for k, v in oracle.pf.items() if k != "logstd"}, rc.batch_tensors(case, 0)[0], case["S"], "f32")
+    b = rc.host_batch(case, 0)
+    dout, dls, info = rc.loss_stage64(head.detach().numpy(), pf.state_dict()["logstd"].numpy().reshape(-1), b["acts"].astype(np.float32),
+                                      b["advs"].astype(np.float32).reshape(-1), case["A"], rc.ENTROPY_COEFF, False)
+    assert dout.shape == (513, 12) and torch.isfinite(dout).all() and torch.isfinite(dls).all()
+    assert np.isfinite(list(info.values())).all()
+    assert dls[0].item() == 0.0 and dls[-1].item() == 0.0 and (dls[1:-1] != 0).all()
+
+
 def test_abi_header_exports_and_mirror():
     from vision4leg_amd import _lib
     hdr = open(os.path.join(util.ROOT, "include", "v4l_hip.h")).read()

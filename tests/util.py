@@ -132,6 +132,36 @@ def spread_policy_head(pf, logstd=None):
     return logstd, bias
 
 
+# ---- A2C's and REINFORCE's test_loss_rows (tests/test_gpu_a2c.py, test_gpu_reinforce.py) and their CPU-side checks
+def loss_rows_case(cases, param):
+    """"name" -> cases[name]; "name@B" -> that geometry at batch size B. "<learner>_mlp_odd@513" (A = 12: the capacity-16 loss
+    code) is the smallest odd row count at which the single-block loss kernels run 1024 threads — sixteen waves' partial sums
+    in the log sigma reduction, a partial last wave. (V-MPO's loss runs on the better half, ceil(B / 2) rows: it would take
+    "@1025"; tests/test_gpu_vmpo.py has no such case yet)"""
+    name, _, b = param.partition("@")
+    return dict(cases[name], B=int(b)) if b else cases[name]
+
+
+def loss_rows_logstd(A, tanh, both_ends=False):
+    """Distinct log sigmas for one loss evaluation. A Normal policy's last one lies beyond LOG_SIG_MAX (sigma = e^2, gradient
+    gated to 0); both_ends: its first one below LOG_SIG_MIN as well (sigma = e^-5). A tanh policy stays at sigma <= 1."""
+    logstd = np.linspace(-1.0, 0.0 if tanh else 0.5, A).astype(np.float32)
+    if not tanh:
+        logstd[-1] = 2.5
+        if both_ends:
+            logstd[0] = -5.5
+    return logstd
+
+
+def loss_rows_both_ends(param, mode, tanh):
+    """Whether a test_loss_rows parameter pins the clamp gate at both ends: the wide-block case of a Normal policy, in f32.
+    A column at sigma = e^-5 multiplies a head-output distance by 1 / sigma^2 = 2.2e4 in the d(mean) rows and in log pi, which
+    the 16-bit modes' bounds (sized for O(1) sigmas) do not cover, and under V4L_F16 the scaled rows leave the operand range
+    (|an d| / sigma^2 * 2^4 > 32768 from |an d| = 0.09 on: 498 of the 513 rows of a2c_mlp_odd@513). The loss kernels are not
+    instantiated per operand type, so the gate the f32 run pins is the code the 16-bit modes run."""
+    return "@" in param and mode == "f32" and not tanh
+
+
 def small_param_names(pf_sd, vf_sd, limit=4096):
     return {(tag, k) for tag, sd in (("pf", pf_sd), ("vf", vf_sd)) for k, v in sd.items() if v.numel() <= limit}
 

@@ -2664,20 +2664,17 @@ static int launch_vmpo_loss(hipStream_t s, const ActorArgs& aa, const VmpoArgs& 
   return 0;
 }
 
-// REINFORCE: the single-block loss launch (csrc/elem.h)
-template <int CAP>
-static int launch_reinforce_loss(hipStream_t s, const ActorArgs& aa, const UpdCtl* ctl, float* rst_all, dim3 blk) {
-  if (aa.tanh_action) V4L_KLAUNCH("reinforce_loss", 0, s, (reinforce_loss_kernel<true, CAP>), dim3(1), blk, 0, s, aa, ctl, rst_all);
-  else V4L_KLAUNCH("reinforce_loss", 0, s, (reinforce_loss_kernel<false, CAP>), dim3(1), blk, 0, s, aa, ctl, rst_all);
-  V4L_LAUNCH_CHECK();
-  return 0;
-}
-
-// A2C: the policy's single-block loss launch (csrc/elem.h)
-template <int CAP>
-static int launch_a2c_loss(hipStream_t s, const ActorArgs& aa, const UpdCtl* ctl, float* ast_all, dim3 blk) {
-  if (aa.tanh_action) V4L_KLAUNCH("a2c_loss", 0, s, (a2c_loss_kernel<true, CAP>), dim3(1), blk, 0, s, aa, ctl, ast_all);
-  else V4L_KLAUNCH("a2c_loss", 0, s, (a2c_loss_kernel<false, CAP>), dim3(1), blk, 0, s, aa, ctl, ast_all);
+// A2C and REINFORCE: the policy's single-block loss launch (csrc/elem.h), 1024 threads from 512 rows on. Both kernel families
+// have one signature; `family` holds a family's four instantiations: TANH is compiled in for TanhNormal policies, and the per-row
+// code holds its per-dimension state per thread, so CAP is 8 for every A <= 8 and V4L_MAX_ACT above.
+static inline dim3 loss_block(int n) { return dim3(n >= 512 ? 1024 : 256); }
+typedef void (*RecLossKernel)(ActorArgs, const UpdCtl*, float*);
+#define V4L_LOSS_FAMILY(kern) \
+  { kern<false, ACT_CAP_NARROW>, kern<false, V4L_MAX_ACT>, kern<true, ACT_CAP_NARROW>, kern<true, V4L_MAX_ACT> }
+static int launch_rec_loss(const char* label, const RecLossKernel (&family)[4], hipStream_t s, const ActorArgs& aa, const UpdCtl* ctl,
+                           float* rec_all) {
+  const RecLossKernel kern = family[(aa.tanh_action ? 2 : 0) + (act_cap(aa.A) != ACT_CAP_NARROW ? 1 : 0)];
+  V4L_KLAUNCH(label, 0, s, kern, dim3(1), loss_block(aa.n), 0, s, aa, ctl, rec_all);
   V4L_LAUNCH_CHECK();
   return 0;
 }
@@ -3533,6 +3530,36 @@ static int check_update_args(const v4l_trainer* tr, const v4l_rollout* ro, int n
   return 0;
 }
 
+// ---- the pieces the A2C and REINFORCE stages are put together from (the PPO and V-MPO stages below spell theirs out: DESIGN.md 7)
+// An update's opening launch, as in v4l_trainer_critic_grads: selects the rows of this update, clears the statistics record, advances Adam's step,
+// advantage statistics (block 0) and refreshes `net`'s packed weights (the other blocks): the critic's, or the policy's where no
+// critic runs.
+static int launch_begin_pack(v4l_trainer* tr, v4l_net* net, const v4l_rollout* ro, int n, hipStream_t s) {
+  g_op = "ctl";
+  return by_compute(net->cfg.compute, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type T;
+    V4L_KLAUNCH("begin_pack", 0, s, begin_pack_kernel<T>, dim3((unsigned)net->pack_blocks + 1), dim3(256), 0, s, tr->ctl, tr->rowidx_all, n,
+                tr->rowidx_cur, tr->stats_cur, ro->advs_dev, net->d_packs, (int)net->packs.size(), (T*)net->packed);
+    V4L_LAUNCH_CHECK();
+    return 0;
+  });
+}
+// The loss launch's arguments for `rows` rows of the policy's forward read through rowidx, a log sigma per action column and no
+// target policy (tmean, tlogstd, logp_old, clip stay zero); the stage sets ent_coef.
+static ActorArgs actor_args(const v4l_trainer* tr, const v4l_rollout* ro, int rows, const int* rowidx) {
+  v4l_net* pf = tr->pf;
+  const Layout Lp = pf->layout(rows);
+  ActorArgs aa;
+  memset(&aa, 0, sizeof(aa));
+  aa.mean = tr->ws + Lp.out; aa.logstd = pf->p[pf->logstd];
+  aa.acts = ro->acts_dev; aa.adv = ro->advs_dev; aa.rowidx = rowidx;
+  aa.n = rows; aa.A = pf->cfg.out_dim; aa.inv_n = 1.f / (float)rows;
+  aa.dmean = tr->ws + Lp.dout; aa.dlogstd = tr->g_pf + pf->params[pf->logstd].goff; aa.st = tr->stats_cur;
+  aa.tanh_action = pf->cfg.tanh_action;
+  aa.gscale = v4l_net_grad_scale(pf, rows);
+  return aa;
+}
+
 int v4l_trainer_critic_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, void* stream) {
   int rc = check_update_args(tr, ro, n, hp);
   if (rc) return rc;
@@ -4193,21 +4220,12 @@ static int a2c_critic_stage(v4l_trainer* tr, const v4l_rollout* ro, int n, const
   v4l_net* vf = tr->vf;
   float* st = tr->stats_cur;
   const int* rowidx = tr->rowidx_cur;
-  g_op = "ctl";
-  if ((rc = by_compute(vf->cfg.compute, [&](auto tag) -> int {
-        typedef typename decltype(tag)::type T;
-        V4L_KLAUNCH("begin_pack", 0, s, begin_pack_kernel<T>, dim3((unsigned)vf->pack_blocks + 1), dim3(256), 0, s, tr->ctl, tr->rowidx_all, n,
-                    tr->rowidx_cur, st, ro->advs_dev, vf->d_packs, (int)vf->packs.size(), (T*)vf->packed);
-        V4L_LAUNCH_CHECK();
-        return 0;
-      })))
-    return rc;
+  if ((rc = launch_begin_pack(tr, vf, ro, n, s))) return rc;
   { PhaseScope ps("vf.fwd");
   if ((rc = v4l_net_forward(vf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, 1, stream))) return rc; }
   const Layout L = vf->layout(n);
   g_op = "loss";
-  const dim3 blk(n >= 512 ? 1024 : 256);
-  V4L_KLAUNCH("a2c_critic_loss", 0, s, a2c_critic_loss_kernel, dim3(1), blk, 0, s, tr->ws + L.out, ro->rets_dev, rowidx, n, 1.f / (float)n,
+  V4L_KLAUNCH("a2c_critic_loss", 0, s, a2c_critic_loss_kernel, dim3(1), loss_block(n), 0, s, tr->ws + L.out, ro->rets_dev, rowidx, n, 1.f / (float)n,
               tr->ws + L.dout, st, v4l_net_grad_scale(vf, n), (const UpdCtl*)tr->ctl, astats_all_dev);
   V4L_LAUNCH_CHECK();
   PhaseScope ps("vf.bwd");
@@ -4219,25 +4237,13 @@ static int a2c_actor_stage(v4l_trainer* tr, const v4l_rollout* ro, int n, const 
   hipStream_t s = (hipStream_t)stream;
   v4l_net* pf = tr->pf;
   const int* rowidx = tr->rowidx_cur;
-  const Layout Lp = pf->layout(n);
   if ((rc = v4l_net_pack(pf, stream))) return rc;  // the previous update's policy step moved the weights
   { PhaseScope ps("pf.fwd");
   if ((rc = v4l_net_forward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, 1, stream))) return rc; }
   g_op = "loss";
-  {
-    ActorArgs aa;
-    memset(&aa, 0, sizeof(aa));
-    aa.mean = tr->ws + Lp.out; aa.logstd = pf->p[pf->logstd];
-    aa.acts = ro->acts_dev; aa.adv = ro->advs_dev; aa.rowidx = rowidx;
-    aa.n = n; aa.A = pf->cfg.out_dim; aa.inv_n = 1.f / (float)n; aa.ent_coef = hp->entropy_coeff;
-    aa.dmean = tr->ws + Lp.dout; aa.dlogstd = tr->g_pf + pf->params[pf->logstd].goff; aa.st = tr->stats_cur;
-    aa.tanh_action = pf->cfg.tanh_action;
-    aa.gscale = v4l_net_grad_scale(pf, n);
-    const dim3 blk(n >= 512 ? 1024 : 256);
-    rc = act_cap(aa.A) != ACT_CAP_NARROW ? launch_a2c_loss<V4L_MAX_ACT>(s, aa, tr->ctl, astats_all_dev, blk)
-                                         : launch_a2c_loss<ACT_CAP_NARROW>(s, aa, tr->ctl, astats_all_dev, blk);
-    if (rc) return rc;
-  }
+  ActorArgs aa = actor_args(tr, ro, n, rowidx);
+  aa.ent_coef = hp->entropy_coeff;
+  if ((rc = launch_rec_loss("a2c_loss", V4L_LOSS_FAMILY(a2c_loss_kernel), s, aa, tr->ctl, astats_all_dev))) return rc;
   PhaseScope ps("pf.bwd");
   return v4l_net_backward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, tr->g_pf, stream);
 }
@@ -4395,35 +4401,14 @@ static int reinforce_actor_stage(v4l_trainer* tr, const v4l_rollout* ro, int n, 
   hipStream_t s = (hipStream_t)stream;
   v4l_net* pf = tr->pf;
   const int* rowidx = tr->rowidx_cur;
-  g_op = "ctl";
-  // v4l_trainer_critic_grads' opening launch with the policy's packs in the critic's place: rows, cleared record, Adam step
-  // sizes and advantage statistics (block 0) next to the weight copies the previous policy step outdated (the other blocks)
-  if ((rc = by_compute(pf->cfg.compute, [&](auto tag) -> int {
-        typedef typename decltype(tag)::type T;
-        V4L_KLAUNCH("begin_pack", 0, s, begin_pack_kernel<T>, dim3((unsigned)pf->pack_blocks + 1), dim3(256), 0, s, tr->ctl, tr->rowidx_all, n,
-                    tr->rowidx_cur, tr->stats_cur, ro->advs_dev, pf->d_packs, (int)pf->packs.size(), (T*)pf->packed);
-        V4L_LAUNCH_CHECK();
-        return 0;
-      })))
-    return rc;
-  const Layout Lp = pf->layout(n);
+  // the opening launch with the policy's packs in the critic's place: the weight copies the previous policy step outdated
+  if ((rc = launch_begin_pack(tr, pf, ro, n, s))) return rc;
   { PhaseScope ps("pf.fwd");
   if ((rc = v4l_net_forward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, 1, stream))) return rc; }
   g_op = "loss";
-  {
-    ActorArgs aa;
-    memset(&aa, 0, sizeof(aa));
-    aa.mean = tr->ws + Lp.out; aa.logstd = pf->p[pf->logstd];
-    aa.acts = ro->acts_dev; aa.adv = ro->advs_dev; aa.rowidx = rowidx;
-    aa.n = n; aa.A = pf->cfg.out_dim; aa.inv_n = 1.f / (float)n; aa.ent_coef = hp->entropy_coeff;
-    aa.dmean = tr->ws + Lp.dout; aa.dlogstd = tr->g_pf + pf->params[pf->logstd].goff; aa.st = tr->stats_cur;
-    aa.tanh_action = pf->cfg.tanh_action;
-    aa.gscale = v4l_net_grad_scale(pf, n);
-    const dim3 blk(n >= 512 ? 1024 : 256);
-    rc = act_cap(aa.A) != ACT_CAP_NARROW ? launch_reinforce_loss<V4L_MAX_ACT>(s, aa, tr->ctl, rstats_all_dev, blk)
-                                         : launch_reinforce_loss<ACT_CAP_NARROW>(s, aa, tr->ctl, rstats_all_dev, blk);
-    if (rc) return rc;
-  }
+  ActorArgs aa = actor_args(tr, ro, n, rowidx);
+  aa.ent_coef = hp->entropy_coeff;
+  if ((rc = launch_rec_loss("reinforce_loss", V4L_LOSS_FAMILY(reinforce_loss_kernel), s, aa, tr->ctl, rstats_all_dev))) return rc;
   PhaseScope ps("pf.bwd");
   return v4l_net_backward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, tr->g_pf, stream);
 }
