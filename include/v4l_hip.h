@@ -305,7 +305,14 @@ int v4l_actor_step_split(v4l_actor* a, const float* proprio_dev, const void* ima
  * slot holds a number or `poll_seconds` have passed. Returns 0: both outputs have arrived — every block has finished reading
  * the staging blocks, they may be overwritten; 1: not waited for (poll_seconds <= 0) or timed out — synchronise the stream
  * before touching the buffers; < 0: error. v4l_host_cast_rows is the cast alone (no GPU involved; compute V4L_F32: image_out
- * is fp32); v4l_host_cast_simd: 1 when the AVX-512 path is in use. */
+ * is fp32); v4l_host_cast_simd: 1 when the AVX-512 path is in use.
+ * The pool is one per process and owns the job it works on (no worker ever reads a caller's stack); it grows to the largest
+ * `threads` - 1 asked for so far and never shrinks: a call with fewer `threads` is worked on by that many participants, the other
+ * workers stay idle, so two handles with different counts cost no thread start per step. Two numbers bear on `threads`:
+ * V4L_CAST_MAX_THREADS is the most threads that ever cast one job, and the Python shell clamps to it before it calls
+ * (_lib.clamp_cast_threads); both entry points keep their argument check and refuse a count outside [1, 256], so a direct C
+ * caller that passes 65 .. 256 is not refused: its job is cast by V4L_CAST_MAX_THREADS threads, silently. */
+#define V4L_CAST_MAX_THREADS 64
 int v4l_host_cast_rows(const double* rows_host, int64_t ld, int E, int S, int64_t img_elems, float* proprio_out, void* image_out,
                        int compute, int threads);
 int v4l_host_cast_simd(void);

@@ -228,23 +228,41 @@ def test_library_host_cast_equals_torch_two_step_rounding(mode, threads):
     assert L.v4l_host_cast_simd() in (0, 1)
 
 
-def test_cast_pool_is_clean_under_thread_sanitizer(tmp_path):
-    """The host thread pool behind v4l_actor_step_rows (csrc/host_step.h: workers that spin, sleep and wake, claim flags, a job
-    object on the caller's stack) under ThreadSanitizer: tools/host/cast_pool_check.cpp runs jobs with changing thread counts,
-    pool resizes and pauses longer than the workers' spin window, and compares every element with the scalar two-step rounding."""
+def _cast_pool_check(tmp_path, sanitizer_flags, name):
+    """tools/host/cast_pool_check.cpp built with `sanitizer_flags`, once as it is and once with the stall macro (a worker sleeps
+    0 - 200 us before it registers for a job: late workers on nearly every job): -> the two finished runs of 90 iterations."""
     import shutil, subprocess
     cxx = os.environ.get("CXX", "/opt/rocm/lib/llvm/bin/clang++")
     if not os.path.exists(cxx) and shutil.which(cxx) is None:
         pytest.skip("no clang++ for the sanitizer build")
-    exe = str(tmp_path / "cast_check_tsan")
     src = os.path.join(os.path.dirname(__file__), "..", "tools", "host", "cast_pool_check.cpp")
-    b = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-fno-omit-frame-pointer", "-pthread", src, "-o", exe],
-                       capture_output=True, text=True)
-    if b.returncode != 0 and "sanitizer" in (b.stderr or "").lower():
-        pytest.skip("this toolchain has no ThreadSanitizer runtime")
-    assert b.returncode == 0, b.stderr[-2000:]
-    r = subprocess.run([exe, "90"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "OK" in r.stdout and "WARNING: ThreadSanitizer" not in r.stderr, (r.stdout[-500:], r.stderr[-3000:])
+    runs = []
+    for tag, stall in (("", []), ("_stall", ["-DV4L_CAST_POOL_TEST_STALL"])):
+        exe = str(tmp_path / ("cast_check_" + name + tag))
+        b = subprocess.run([cxx, "-std=c++17", "-O1", "-g", *sanitizer_flags, *stall, "-fno-omit-frame-pointer", "-pthread", src, "-o", exe],
+                           capture_output=True, text=True)
+        if b.returncode != 0 and "sanitizer" in (b.stderr or "").lower():
+            pytest.skip("this toolchain has no %s runtime" % name)
+        assert b.returncode == 0, b.stderr[-2000:]
+        runs.append(subprocess.run([exe, "90"], capture_output=True, text=True, timeout=600))
+    return runs
+
+
+def test_cast_pool_is_clean_under_thread_sanitizer(tmp_path):
+    """The host thread pool behind v4l_actor_step_rows (csrc/host_step.h: workers that spin, sleep and wake, claim flags, a job
+    slot the pool owns, opened and closed around every job) under ThreadSanitizer: tools/host/cast_pool_check.cpp runs jobs with
+    changing thread counts from changing stack depths, a pool that grows and never shrinks (4 and 7 threads: 6 workers) and pauses
+    longer than the workers' spin window, and compares every element with the scalar two-step rounding; a second build makes the
+    workers register late."""
+    for r in _cast_pool_check(tmp_path, ["-fsanitize=thread"], "ThreadSanitizer"):
+        assert r.returncode == 0 and "OK" in r.stdout and "WARNING: ThreadSanitizer" not in r.stderr, (r.stdout[-500:], r.stderr[-3000:])
+
+
+def test_cast_pool_is_clean_under_address_sanitizer(tmp_path):
+    """The same program and the same two builds under AddressSanitizer with every frame's locals on the detectable fake stack: a
+    worker that reached into a caller's frame after the call had returned would be a stack-use-after-return report."""
+    for r in _cast_pool_check(tmp_path, ["-fsanitize=address", "-fsanitize-address-use-after-return=always"], "AddressSanitizer"):
+        assert r.returncode == 0 and "OK" in r.stdout and "ERROR: AddressSanitizer" not in r.stderr, (r.stdout[-500:], r.stderr[-3000:])
 
 
 def test_replay_buffer_iteration_matches_reference_semantics():
@@ -301,6 +319,16 @@ def test_cast_threads_env_is_validated(monkeypatch):
         coll._cast_threads_from_env()
     monkeypatch.setenv("V4L_CAST_THREADS", "3")
     assert coll._cast_threads_from_env() == 3
+
+
+def test_cast_thread_count_is_clamped_to_the_library_limit():
+    """HipActor.step_host_rows hands _lib.clamp_cast_threads(threads) to the library: V4L_CAST_THREADS=1000 casts on
+    V4L_CAST_MAX_THREADS threads (the constant of include/v4l_hip.h) instead of failing every env step with a bad argument."""
+    from vision4leg_amd import _lib
+    hdr = open(os.path.join(util.ROOT, "include", "v4l_hip.h")).read()
+    assert int(re.search(r"#define V4L_CAST_MAX_THREADS (\d+)", hdr).group(1)) == _lib.V4L_CAST_MAX_THREADS == 64
+    assert [_lib.clamp_cast_threads(n) for n in (1, 8, 64, 65, 100000)] == [1, 8, 64, 64, 64]
+    assert _lib.clamp_cast_threads(0) == 1
 
 
 def test_device_identity_ignores_visibility_strings_when_the_gpu_is_identified(monkeypatch):

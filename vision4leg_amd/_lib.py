@@ -26,6 +26,12 @@ V4L_A2C_STATS = 16    # floats per update in the A2C record (include/v4l_hip.h)
 V4L_REINFORCE_STATS = 12   # floats per update in the REINFORCE record (include/v4l_hip.h)
 V4L_BUCKET_TAIL = 8   # scalars behind the gradients of an all-reduce bucket
 V4L_COMM_ID_BYTES = 128
+V4L_CAST_MAX_THREADS = 64   # most host threads that cast one job's rows (include/v4l_hip.h)
+
+
+def clamp_cast_threads(threads):
+  """The thread count handed to v4l_actor_step_rows: any integer -> [1, V4L_CAST_MAX_THREADS]."""
+  return max(1, min(int(threads), V4L_CAST_MAX_THREADS))
 
 # order of the 18 logger keys inside a stats record (torchrl/algo/on_policy/ppo.py:77-92,122-123,142-145)
 STAT_KEYS = [

@@ -19,10 +19,10 @@
 #include <cstring>
 #include <mutex>
 #include <thread>
-#include <vector>
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
+#include "../../include/v4l_hip.h"
 
 namespace v4l {
 namespace host {
@@ -113,16 +113,19 @@ static inline void cast_span_f32(const double* src, float* dst, int64_t n, bool 
 // per unit — a first version with a shared "next unit" word scaled to 3.3 x on 8 threads and got SLOWER beyond 16); a participant
 // that finishes early walks the other parts and takes any that nobody has claimed yet (a worker that was asleep).
 constexpr int64_t CAST_CHUNK = 2048;
-constexpr int CAST_MAX_PARTS = 64;
-struct alignas(64) CastClaim { std::atomic<int> taken{0}; };
-struct CastJob {
+constexpr int CAST_MAX_PARTS = V4L_CAST_MAX_THREADS;
+struct CastParams {
   const double* rows; int64_t ld; int E, S; int64_t img;
   float* prop; void* img_out; int kind; bool simd;
   int units, parts;
+};
+struct alignas(64) CastClaim { std::atomic<int> taken{0}; };
+struct CastJob {
+  CastParams p;
   CastClaim claim[CAST_MAX_PARTS];
   alignas(64) std::atomic<int> done{0};  // parts finished
 };
-static inline void cast_unit(const CastJob& j, int u) {
+static inline void cast_unit(const CastParams& j, int u) {
   const int64_t per_row = (j.img + CAST_CHUNK - 1) / CAST_CHUNK;
   const int e = (int)(u / per_row);
   const int64_t c0 = (u - (int64_t)e * per_row) * CAST_CHUNK, c1 = c0 + CAST_CHUNK < j.img ? c0 + CAST_CHUNK : j.img;
@@ -131,110 +134,120 @@ static inline void cast_unit(const CastJob& j, int u) {
   if (j.kind == 0) cast_span_f32(src + j.S + c0, reinterpret_cast<float*>(j.img_out) + (int64_t)e * j.img + c0, c1 - c0, j.simd);
   else cast_span(src + j.S + c0, reinterpret_cast<uint16_t*>(j.img_out) + (int64_t)e * j.img + c0, c1 - c0, j.kind, j.simd);
 }
-// participant `id` (0 = the caller, 1.. = workers): its own part first, then whatever is still unclaimed
+// participant `id` (0 = the caller, 1 .. parts - 1 = workers): its own part first, then whatever is still unclaimed
 static inline void cast_drain(CastJob& j, int id) {
-  for (int k = 0; k < j.parts; ++k) {
-    const int p = (id + k) % j.parts;
+  const int parts = j.p.parts, units = j.p.units;
+  for (int k = 0; k < parts; ++k) {
+    const int p = (id + k) % parts;
     if (j.claim[p].taken.load(std::memory_order_relaxed) != 0 || j.claim[p].taken.exchange(1, std::memory_order_acq_rel) != 0) continue;
-    const int u0 = (int)((int64_t)j.units * p / j.parts), u1 = (int)((int64_t)j.units * (p + 1) / j.parts);
-    for (int u = u0; u < u1; ++u) cast_unit(j, u);
+    const int u0 = (int)((int64_t)units * p / parts), u1 = (int)((int64_t)units * (p + 1) / parts);
+    for (int u = u0; u < u1; ++u) cast_unit(j.p, u);
     j.done.fetch_add(1, std::memory_order_release);
   }
 }
 
+// The pool lives as long as the process: it only ever gains workers, they are detached and keep `this`, so the one instance
+// is never destroyed and no other can be made.
 class CastPool {
  public:
   static constexpr int64_t SPIN_NS = 300000;  // a worker keeps spinning this long after its last job, then sleeps
-  explicit CastPool(int workers) {
-    for (int i = 0; i < workers; ++i) th_.emplace_back([this, i] { loop(i + 1); });
+  static CastPool& instance() { static CastPool* pool = new CastPool; return *pool; }
+  int workers() const { return workers_; }    // threads started so far
+  // (call between jobs) starts workers until there are `workers` of them; the ones already running stay
+  void grow(int workers) {
+    for (; workers_ < workers; ++workers_)
+      std::thread([this, id = workers_ + 1, seen = state_.load(std::memory_order_relaxed) >> 1] { loop(id, seen); }).detach();
   }
-  ~CastPool() {
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      stop_.store(true, std::memory_order_release);
-      gen_.fetch_add(1, std::memory_order_release);
-    }
-    cv_.notify_all();
-    for (std::thread& t : th_) t.join();
-  }
-  int workers() const { return (int)th_.size(); }
-  // runs the job on the pool's workers + the calling thread; returns when every unit is done
-  void run(CastJob& j) {
-    job_.store(&j, std::memory_order_release);
-    gen_.fetch_add(1, std::memory_order_release);
-    if (sleepers_.load(std::memory_order_acquire) > 0) {
+  // runs the job on the workers 1 .. p.parts - 1 + the calling thread; returns when every unit is done and no worker is inside
+  void run(const CastParams& p) {
+    job_.p = p;
+    for (int i = 0; i < p.parts; ++i) job_.claim[i].taken.store(0, std::memory_order_relaxed);
+    job_.done.store(0, std::memory_order_relaxed);
+    const uint64_t gen = (state_.load(std::memory_order_relaxed) >> 1) + 1;
+    state_.store(gen << 1 | 1, std::memory_order_seq_cst);  // open: the next generation and its job in one write
+    if (sleepers_.load(std::memory_order_seq_cst) > 0) {
       std::lock_guard<std::mutex> g(mu_);
       cv_.notify_all();
     }
-    cast_drain(j, 0);
-    while (j.done.load(std::memory_order_acquire) < j.parts) cpu_relax();
-    job_.store(nullptr, std::memory_order_release);
-    // (a worker that read the pointer before it was cleared finds every part claimed and touches nothing else of the job; the
-    // job object must outlive that look: busy_ counts the workers inside a job)
-    while (busy_.load(std::memory_order_acquire) > 0) cpu_relax();
+    cast_drain(job_, 0);
+    while (job_.done.load(std::memory_order_acquire) < p.parts) cpu_relax();
+    state_.store(gen << 1, std::memory_order_seq_cst);  // close
+    while (busy_.load(std::memory_order_seq_cst) > 0) cpu_relax();
   }
 
  private:
-  void loop(int id) {
-    uint64_t seen = 0;
+  CastPool() = default;
+  void loop(int id, uint64_t seen) {
+    uint64_t spins = 0;
+#ifdef V4L_CAST_POOL_TEST_STALL
+    uint64_t lcg = 0x9e3779b97f4a7c15ull * (uint64_t)id;
+#endif
     auto last = std::chrono::steady_clock::now();
     for (;;) {
-      const uint64_t g = gen_.load(std::memory_order_acquire);
+      const uint64_t g = state_.load(std::memory_order_acquire) >> 1;
       if (g != seen) {
         seen = g;
-        if (stop_.load(std::memory_order_acquire)) return;
-        busy_.fetch_add(1, std::memory_order_acq_rel);
-        CastJob* j = job_.load(std::memory_order_acquire);
-        if (j != nullptr) cast_drain(*j, id);
+#ifdef V4L_CAST_POOL_TEST_STALL  // (tools/host/cast_pool_check.cpp only) a late worker on nearly every job: 0 - 200 us before it registers
+        lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+        std::this_thread::sleep_for(std::chrono::microseconds((lcg >> 33) % 201));
+#endif
+        busy_.fetch_add(1, std::memory_order_seq_cst);
+        const uint64_t s = state_.load(std::memory_order_seq_cst);
+        seen = s >> 1;  // (a late worker may find a LATER job open: that is the generation it has now dealt with)
+        if ((s & 1) != 0 && id < job_.p.parts) cast_drain(job_, id);
         busy_.fetch_sub(1, std::memory_order_acq_rel);
         last = std::chrono::steady_clock::now();
         continue;
       }
       cpu_relax();
-      if ((++spins_ & 1023) == 0 &&
+      if ((++spins & 1023) == 0 &&
           std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - last).count() > SPIN_NS) {
         std::unique_lock<std::mutex> lk(mu_);
-        sleepers_.fetch_add(1, std::memory_order_acq_rel);
-        cv_.wait(lk, [&] { return gen_.load(std::memory_order_acquire) != seen; });
+        sleepers_.fetch_add(1, std::memory_order_seq_cst);
+        cv_.wait(lk, [&] { return state_.load(std::memory_order_seq_cst) >> 1 != seen; });
         sleepers_.fetch_sub(1, std::memory_order_acq_rel);
       }
     }
   }
-  std::vector<std::thread> th_;
+  // The one job slot (jobs are strictly sequential: pool_mutex()) and its state word: generation << 1 | open. A job is open
+  // from run()'s first store of state_ to its second. Invariant: a worker reads or claims anything in job_ only between its busy_
+  // increment and decrement AND after it has read the open bit set in between; run() writes job_'s plain fields only while the
+  // bit is clear and after it has read busy_ == 0 since clearing it. Close -> read busy_ on the caller's side and register ->
+  // read state_ on the worker's side are store-then-load pairs, so all four are seq_cst: in their single total order either the
+  // caller sees the worker and waits for it, or the worker sees the job closed and leaves (or sees a LATER job open — whose
+  // store it then acquires, fields and all, and whose run() finds it in busy_; it takes that reading's generation as seen, so it
+  // does not register for the same job twice). Open -> read sleepers_ against count myself -> read state_ (a worker going to
+  // sleep) is the same pattern and seq_cst for the same reason.
+  // A cache line each for what the idle workers spin on (state_) and what every participant increments and decrements per job
+  // (busy_): on one line, each of those 14 writes per job took the line from every spinner, and on a two-socket host a process
+  // ran 6.6 - 7.5 or 9 - 11 us per job depending on where its threads had landed (profiles/cast_pool_timing.txt).
+  CastJob job_;
+  alignas(64) std::atomic<uint64_t> state_{0};
+  alignas(64) std::atomic<int> busy_{0};
+  alignas(64) std::atomic<int> sleepers_{0};
   std::mutex mu_;
   std::condition_variable cv_;
-  std::atomic<uint64_t> gen_{0};
-  std::atomic<CastJob*> job_{nullptr};
-  std::atomic<int> busy_{0}, sleepers_{0};
-  std::atomic<bool> stop_{false};
-  static thread_local uint64_t spins_;
+  int workers_ = 0;
 };
-thread_local uint64_t CastPool::spins_ = 0;
 
-// process-wide pool, resized on demand (threads - 1 workers: the caller works too). One job at a time: the library's contract is
-// one HANDLE per host thread at a time, but the pool is shared by all handles of the process — two collectors in two threads
-// take turns here (uncontended: one atomic exchange).
+// process-wide pool (threads - 1 workers: the caller works too), grown to the largest count asked for so far and never shrunk:
+// a job with fewer parts leaves the workers beyond them idle. One job at a time: the library's contract is one HANDLE per host
+// thread at a time, but the pool is shared by all handles of the process — two collectors in two threads take turns here
+// (uncontended: one atomic exchange).
 static std::mutex& pool_mutex() { static std::mutex mu; return mu; }
-static CastPool* pool_for(int threads) {  // (call with pool_mutex() held)
-  static CastPool* pool = nullptr;
-  const int want = threads > 1 ? threads - 1 : 0;
-  if (pool == nullptr || pool->workers() != want) {
-    delete pool;
-    pool = new CastPool(want);
-  }
-  return pool;
-}
 
 static int cast_rows(const double* rows, int64_t ld, int E, int S, int64_t img, float* prop, void* img_out, int kind, int threads) {
-  CastJob j;
-  j.rows = rows; j.ld = ld; j.E = E; j.S = S; j.img = img; j.prop = prop; j.img_out = img_out; j.kind = kind;
-  j.simd = have_avx512();
-  j.units = E * (int)((img + CAST_CHUNK - 1) / CAST_CHUNK);
+  CastParams p = {rows, ld, E, S, img, prop, img_out, kind, have_avx512(), E * (int)((img + CAST_CHUNK - 1) / CAST_CHUNK), 1};
   if (threads > CAST_MAX_PARTS) threads = CAST_MAX_PARTS;
-  j.parts = threads < 1 ? 1 : (threads > j.units ? j.units : threads);
-  if (j.parts <= 1) { cast_drain(j, 0); return 0; }
+  if (threads > p.units) threads = p.units;
+  if (threads <= 1) {
+    for (int u = 0; u < p.units; ++u) cast_unit(p, u);
+    return 0;
+  }
+  p.parts = threads;
   std::lock_guard<std::mutex> g(pool_mutex());
-  pool_for(j.parts)->run(j);
+  CastPool::instance().grow(p.parts - 1);
+  CastPool::instance().run(p);
   return 0;
 }
 

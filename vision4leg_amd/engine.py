@@ -979,7 +979,7 @@ class HipActor:
     this actor's pinned staging blocks (fp32 proprio | 16-bit depth stack: the same two roundings as torch.Tensor(ob) followed by
     the kernels' ingest), issues the step's two launches on them and watches the pinned action / value buffers fill. No torch
     call and no Python loop per step. Returns the [E][A] action as a numpy view of pinned memory (valid until the next step).
-    Needs split_supported(); eager launches only."""
+    `threads` is clamped to [1, V4L_CAST_MAX_THREADS]. Needs split_supported(); eager launches only."""
     if self.graph:
       raise RuntimeError("vision4leg_amd: step_host_rows drives eager launches (construct the actor with graph=False)")
     S, img = self.pf.state_dim, self.pf.img_elems
@@ -1016,7 +1016,7 @@ class HipActor:
       fixed = self._rows_fixed = (a, C.c_void_p(prop.data_ptr()), C.c_void_p(img16.data_ptr()),
                                   C.c_void_p(self._act_host.data_ptr()), C.c_void_p(self._val_host.data_ptr()))
     rc = self.L.v4l_actor_step_rows(self.h, C.c_void_p(rows.__array_interface__["data"][0]), rows.shape[1], fixed[1], fixed[2], eps,
-                                    a[2], a[3], a[4], a[5], a[6], fixed[3], a[8], a[9], a[10], fixed[4], a[12], int(threads),
+                                    a[2], a[3], a[4], a[5], a[6], fixed[3], a[8], a[9], a[10], fixed[4], a[12], _lib.clamp_cast_threads(threads),
                                     self.POLL_SECONDS if self._poll else 0.0, _stream())
     if rc == 1:  # not waited for / timed out: the stream's completion is the step's
       torch.cuda.current_stream(self.device).synchronize()
