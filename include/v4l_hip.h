@@ -162,6 +162,20 @@ int v4l_abi_sizeof(int which);
 
 /* ---- network plan: replaces the nn.Module constructors' shape bookkeeping (nets.py / base.py above) ---- */
 int v4l_net_create(const v4l_net_cfg* cfg, v4l_net** out);
+/* (version 115) Marks a plan as policies.CategoricalDisPolicy (policies/discrete_policies.py:127-172): a networks.Net whose
+ * K = out_dim head outputs are logits, `torch.softmax(logits, -1)` the probabilities of a torch.distributions.Categorical over K
+ * discrete actions. v4l_net_cfg keeps its size and fields: the flag lives in the plan. Valid between v4l_net_create and
+ * v4l_net_bind, on a V4L_NET_MLP net with has_logstd == V4L_LOGSTD_NONE and 2 <= out_dim <= V4L_OUT_LD (the logits fill one
+ * padded head row); anything else fails with a message that names the condition. A flagged net is a policy with no `logstd`
+ * parameter whose action is ONE index, stored as a float in [n][1] action rows: v4l_trainer_create (pf and target_pf both
+ * flagged) and v4l_actor_create take it as pf. It runs under the A2C and REINFORCE updates (a2c.py:61-74 and reinforce.py:52-61
+ * read log_prob and ent only; a2c.py:63-65,97-102 log std/* only `if 'std' in out`), with a2c_cat_loss_kernel /
+ * reinforce_cat_loss_kernel in the Gaussian loss launches' place and the records' std/* slots left as cleared; the PPO and V-MPO
+ * entry points refuse it. Its rollout step is always the GENERAL route (v4l_actor_route) with act_finish_cat_kernel as epilogue:
+ * `eps_dev` of the step entry points then carries [E] uniforms in [0, 1), one per env — the action is the inverse-CDF index of
+ * v4l_cat_sample — or negative numbers for the first argmax (eval_act, discrete_policies.py:156-158); action_dev is [E][1],
+ * mean_dev / std_dev are not written. */
+int v4l_net_set_categorical(v4l_net* net, int on);
 void v4l_net_destroy(v4l_net* net);
 int v4l_net_num_params(const v4l_net* net);
 /* name = the reference state_dict key (SURVEY.md §8b "Checkpoint names"); shape in PyTorch layout */
@@ -225,6 +239,18 @@ int v4l_gauss_head_tanh(const float* out_dev, const float* logstd_dev, const flo
  * log_prob [n]. tanh_action / pre_tanh_dev as in v4l_gauss_head_tanh. 1 <= A <= V4L_OUT_LD / 2. */
 int v4l_gauss_head_sd(const float* out_dev, const float* acts_dev, const float* pre_tanh_dev, int n, int A, int tanh_action,
                       float* mean_dev, float* std_dev, float* logstd_clamped_dev, float* ent_dev, float* logp_dev, void* stream);
+/* CategoricalDisPolicy.{forward,explore,update} post-processing (policies/discrete_policies.py:136-172; version 115):
+ * logits_dev is v4l_net_out_ptr of the policy net ([n][V4L_OUT_LD], columns 0 .. K-1). probs_dev [n][K] = softmax (log-softmax by
+ * max-subtraction, fp32), ent_dev [n] = -sum p log p, and logp_dev [n] = log p of the action indices acts_dev [n] (floats; NaN
+ * for a value that is no integer in [0, K)) when acts_dev != NULL. 2 <= K <= V4L_OUT_LD. Categorical(probs=...)'s clamp of the
+ * probabilities to [eps, 1 - eps] is not applied. */
+int v4l_cat_head(const float* logits_dev, const float* acts_dev, int n, int K, float* probs_dev, float* ent_dev, float* logp_dev,
+                 void* stream);
+/* Categorical(probs).sample() (discrete_policies.py:143-144) by inverse CDF: idx_dev[i] = the first k whose running sum
+ * probs[i][0] + .. + probs[i][k] (fp32, in that order) exceeds u_dev[i], K - 1 if rounding leaves none; u_dev: [n] uniforms in
+ * [0, 1) from the caller's generator (torch.rand: not torch.multinomial's stream). deterministic != 0: the first argmax of the
+ * row (eval_act), u_dev may be NULL. */
+int v4l_cat_sample(const float* probs_dev, const float* u_dev, int n, int K, int deterministic, int64_t* idx_dev, void* stream);
 /* column 0 of a padded head output -> contiguous [n] (vf(x) for the collector, collector/on_policy.py:99-100) */
 int v4l_col0(const float* src_dev, int n, float* dst_dev, void* stream);
 

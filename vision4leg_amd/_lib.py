@@ -71,6 +71,8 @@ VMPO_INFO_KEYS = (STAT_KEYS[:7] + VMPO_STAT_KEYS[:3] + STAT_KEYS[7:11] + VMPO_ST
 # the A2C record's first 12 slots = the keys A2C.update returns, in the reference's order (torchrl/algo/on_policy/a2c.py:89-105)
 A2C_INFO_KEYS = ["Training/policy_loss", "Training/vf_loss", "v_pred/mean", "v_pred/std", "v_pred/max", "v_pred/min",
                  "std/mean", "std/std", "std/max", "std/min", "ent", "log_prob"]
+# the 8 of them a categorical policy leaves: the reference logs std/* only `if 'std' in out` (a2c.py:63-65,97-102)
+A2C_CAT_INFO_KEYS = [k for k in A2C_INFO_KEYS if not k.startswith("std/")]
 
 # the REINFORCE record's first 10 slots = the keys Reinforce.update returns, in the reference's order
 # (torchrl/algo/on_policy/reinforce.py:43-74)
@@ -113,6 +115,7 @@ _SIGS = {
   "v4l_version": (C.c_int, []),
   "v4l_abi_sizeof": (C.c_int, [C.c_int]),
   "v4l_net_create": (C.c_int, [C.POINTER(NetCfg), C.POINTER(_P)]),
+  "v4l_net_set_categorical": (C.c_int, [_P, C.c_int]),
   "v4l_net_destroy": (None, [_P]),
   "v4l_net_num_params": (C.c_int, [_P]),
   "v4l_net_param_info": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int),
@@ -134,6 +137,8 @@ _SIGS = {
   "v4l_gauss_head": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
   "v4l_gauss_head_tanh": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
   "v4l_gauss_head_sd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+  "v4l_cat_head": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
+  "v4l_cat_sample": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
   "v4l_col0": (C.c_int, [_P, C.c_int, _P, _P]),
   "v4l_gae": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                         _P, _P, _P, _P, _P, _P]),

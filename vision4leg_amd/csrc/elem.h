@@ -380,6 +380,105 @@ __global__ __launch_bounds__(256) void act_finish_sd_kernel(ActCtl* c, const flo
                         tanh_action);
 }
 
+// --------------------------------------------------------------------------------- categorical head (discrete actions)
+// CategoricalDisPolicy (policies/discrete_policies.py:127-172): the K = out_dim columns of a padded head row [OUT_LD] are logits;
+// `torch.softmax(logits, -1)` feeds torch.distributions.Categorical. One thread holds a row's K values in registers: the
+// log-softmax by max-subtraction, p_j = exp(z_j - max) / sum, log p_j = z_j - max - log(sum), H = -sum_j p_j log p_j, fp32
+// throughout. Columns K .. 15 come out as p = 0, log p = 0. (Categorical(probs=...) clamps the probabilities to
+// [eps, 1 - eps] before it takes their log: not reproduced, inactive while every p_j lies inside that interval.)
+constexpr int CAT_CAP = OUT_LD;  // 2 <= K <= V4L_OUT_LD (v4l_net_set_categorical)
+struct CatDist { float p[CAT_CAP], lg[CAT_CAP]; float ent; };
+__device__ __forceinline__ CatDist cat_dist(const float* __restrict__ row, int K) {
+  CatDist d;
+  float z[CAT_CAP];
+#pragma unroll
+  for (int q = 0; q < CAT_CAP / 4; ++q) {  // (the rows are 64-byte aligned)
+    const float4 m = *reinterpret_cast<const float4*>(row + 4 * q);
+    z[4 * q] = m.x; z[4 * q + 1] = m.y; z[4 * q + 2] = m.z; z[4 * q + 3] = m.w;
+  }
+  float mx = z[0];
+#pragma unroll
+  for (int j = 1; j < CAT_CAP; ++j)
+    if (j < K) mx = fmaxf(mx, z[j]);
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < CAT_CAP; ++j) {
+    d.p[j] = j < K ? expf(z[j] - mx) : 0.f;
+    s += d.p[j];
+  }
+  const float ls = logf(s);
+  d.ent = 0.f;
+#pragma unroll
+  for (int j = 0; j < CAT_CAP; ++j) {
+    d.lg[j] = j < K ? z[j] - mx - ls : 0.f;
+    d.p[j] = d.p[j] / s;
+    d.ent -= d.p[j] * d.lg[j];
+  }
+  return d;
+}
+// log p of the action index a stored as a float; NaN for anything that is not an integer in [0, K) (register select: no indexing)
+__device__ __forceinline__ float cat_logp(const CatDist& d, int K, float a) {
+  float lp = NAN;
+#pragma unroll
+  for (int j = 0; j < CAT_CAP; ++j)
+    if (j < K && a == (float)j) lp = d.lg[j];
+  return lp;
+}
+// Categorical.sample() by inverse CDF from one uniform u in [0, 1): the first k whose running sum p_0 + .. + p_k exceeds u,
+// K - 1 if rounding leaves none. u < 0: no draw, the first argmax (eval_act, discrete_policies.py:156-158).
+__device__ __forceinline__ int cat_pick(const CatDist& d, int K, float u) {
+  int idx = K - 1;
+  if (u < 0.f) {
+    float best = d.p[0];
+    idx = 0;
+#pragma unroll
+    for (int j = 1; j < CAT_CAP; ++j)
+      if (j < K && d.p[j] > best) { best = d.p[j]; idx = j; }
+    return idx;
+  }
+  float c = 0.f;
+  bool found = false;
+#pragma unroll
+  for (int j = 0; j < CAT_CAP; ++j) {
+    c += d.p[j];
+    if (!found && j < K && c > u) { idx = j; found = true; }
+  }
+  return idx;
+}
+// the same pick from a row of probabilities [K] (v4l_cat_sample: what explore() draws from)
+__global__ __launch_bounds__(256) void cat_sample_kernel(const float* __restrict__ probs, const float* __restrict__ u, int n, int K,
+                                                         int deterministic, long long* __restrict__ idx) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  CatDist d;
+#pragma unroll
+  for (int j = 0; j < CAT_CAP; ++j) d.p[j] = j < K ? probs[(int64_t)i * K + j] : 0.f;
+  idx[i] = cat_pick(d, K, deterministic ? -1.f : u[i]);
+}
+// CategoricalDisPolicy.explore (discrete_policies.py:140-154) + the value read-out of the collector for one env step on the
+// GENERAL route: act_finish_kernel's counterpart. u: [E] uniforms in [0, 1) (negative: argmax). Files the action index (as a
+// float, [E][1] rows), the value and log pi_old, advances t; no mean / std.
+__global__ __launch_bounds__(256) void act_finish_cat_kernel(ActCtl* c, const float* __restrict__ logits,
+                                                             const float* __restrict__ valuep, const float* __restrict__ u, int E,
+                                                             int K, float* __restrict__ acts_roll, float* __restrict__ values_roll,
+                                                             float* __restrict__ logp_roll, float* __restrict__ action,
+                                                             float* __restrict__ ent, float* __restrict__ value) {
+  const long long t = c->t;
+  for (int i = threadIdx.x; i < E; i += 256) {
+    const CatDist d = cat_dist(logits + (int64_t)i * OUT_LD, K);
+    const float act = (float)cat_pick(d, K, u[i]);
+    action[i] = act;
+    ent[i] = d.ent;
+    if (acts_roll != nullptr) acts_roll[t * E + i] = act;
+    const float v = valuep[(int64_t)i * OUT_LD];
+    value[i] = v;
+    if (values_roll != nullptr) values_roll[t * E + i] = v;
+    if (logp_roll != nullptr) logp_roll[t * E + i] = cat_logp(d, K, act);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) c->t = t + 1;
+}
+
 // --------------------------------------------------------------------------------- block reductions
 struct Red4 { double s, s2; float mx, mn; };
 // Block reduction (blockDim.x = 64 * nw, nw <= 16) of (sum, sum of squares, max, min); result valid on all threads.
@@ -954,6 +1053,22 @@ __global__ __launch_bounds__(256) void gauss_head_sd_kernel(const float* __restr
   }
   ent[i] = e;
   if (acts != nullptr) logp[i] = lp;
+}
+
+// Categorical head post-processing for the policy API (CategoricalDisPolicy.forward / explore / update,
+// policies/discrete_policies.py:136-172): from the padded logits [n][OUT_LD] the probabilities [n][K], the entropy [n] and, when
+// acts != null, log_prob [n] of the action indices acts [n] (floats). gauss_head_kernel's counterpart.
+__global__ __launch_bounds__(256) void cat_head_kernel(const float* __restrict__ logits, const float* __restrict__ acts, int n,
+                                                       int K, float* __restrict__ probs, float* __restrict__ ent,
+                                                       float* __restrict__ logp) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const CatDist d = cat_dist(logits + (int64_t)i * OUT_LD, K);
+#pragma unroll
+  for (int j = 0; j < CAT_CAP; ++j)
+    if (j < K) probs[(int64_t)i * K + j] = d.p[j];
+  ent[i] = d.ent;
+  if (acts != nullptr) logp[i] = cat_logp(d, K, acts[i]);
 }
 
 // Copy column 0 of a padded head output to a contiguous [n] vector (critic values for the collector).
@@ -1586,6 +1701,104 @@ __global__ __launch_bounds__(1024) void reinforce_loss_kernel(ActorArgs p, const
     rst[RST_ADV_MAX] = st[ST_ADV_MAX]; rst[RST_ADV_MIN] = st[ST_ADV_MIN];
     rst[RST_PI_LOSS] = loss;
     rst[RST_ENT] = D.ent;
+    rst[RST_LP_MEAN] = (float)lpm;
+    rst[RST_LP_STD] = lps;
+    rst[RST_LP_MAX] = r.mx; rst[RST_LP_MIN] = r.mn;
+  }
+}
+
+// ---- the two losses for CategoricalDisPolicy (policies/discrete_policies.py:160-172: log_prob and entropy of
+// Categorical(softmax(logits))), in a2c_loss_kernel's / reinforce_loss_kernel's launch position with their records, UpdCtl handling
+// and block reductions. p.mean: the logits rows [n][OUT_LD], p.A = K, p.acts: [slots][1] action indices as floats; p.logstd,
+// p.dlogstd, p.tanh_action unused. Per row, with p = softmax(z), H its entropy and an the normalised advantage:
+//   policy_loss = mean_i(-log p_i[a_i] an_i) - ent_coef mean_i(H_i)
+//   d z_j = (1 / n) (-an ([j == a] - p_j) + ent_coef p_j (log p_j + H))       (dH / dz_j = -p_j (log p_j + H))
+// written into the d(out) row scaled and clamped like the Gaussian kernels' (grad_out), columns K .. 15 exactly zero.
+struct CatLossRow { float lp, ent, an; };
+__device__ __forceinline__ CatLossRow cat_loss_row(const ActorArgs& p, int i, float amean, float astd, int& sat) {
+  const int K = p.A;
+  const int slot = p.rowidx ? p.rowidx[i] : i;
+  CatLossRow o;
+  o.an = (p.adv[slot] - amean) / (astd + 1e-5f);
+  const float act = p.acts[slot];
+  const CatDist d = cat_dist(p.mean + (int64_t)i * OUT_LD, K);
+  o.lp = cat_logp(d, K, act);
+  o.ent = d.ent;
+  float dz[CAT_CAP];
+#pragma unroll
+  for (int j = 0; j < CAT_CAP; ++j) {
+    dz[j] = 0.f;
+    if (j < K) {
+      const float hit = act == (float)j ? 1.f : 0.f;
+      dz[j] = grad_out(p.inv_n * (-o.an * (hit - d.p[j]) + p.ent_coef * d.p[j] * (d.lg[j] + d.ent)), p.gscale, sat);
+    }
+  }
+  actor_store_dmean(p.dmean + (int64_t)i * OUT_LD, dz, true);
+  return o;
+}
+// A2C.update's policy loss (a2c.py:61-74) for a categorical policy: fills AST_PI_LOSS, AST_ENT (ent.mean()) and AST_LOGP; the
+// record's std/* slots (a2c.py:97-102 logs them only `if 'std' in out`) stay as the caller cleared them.
+__global__ __launch_bounds__(1024) void a2c_cat_loss_kernel(ActorArgs p, const UpdCtl* __restrict__ ctl, float* __restrict__ ast_all) {
+  const int n = p.n;
+  const float amean = p.st[ST_ADV_MEAN], astd = p.st[ST_ADV_STD];
+  double s_lp = 0.0, s_loss = 0.0, s_ent = 0.0;
+  int sat = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const CatLossRow o = cat_loss_row(p, i, amean, astd, sat);
+    s_loss += (double)(-o.lp * o.an);
+    s_lp += o.lp;
+    s_ent += o.ent;
+  }
+  const Red4 r = block_red4(s_loss, s_lp, 0.f, 0.f);
+  const Red4 r2 = block_red4((double)sat, s_ent, 0.f, 0.f);
+  if (threadIdx.x == 0) {
+    float* st = p.st;
+    const double lpm = r.s2 / n, entm = r2.s2 / n;
+    const float loss = (float)(r.s / n - (double)p.ent_coef * entm);
+    st[ST_PI_LOSS] = loss;
+    st[ST_LP_MEAN] = (float)lpm;
+    if (p.gscale != 1.f) st[ST_F16_SAT] += (float)r2.s;
+    float* ast = ast_all + (int64_t)ctl->upd_index * AST_SIZE;
+    ast[AST_PI_LOSS] = loss;
+    ast[AST_ENT] = (float)entm;
+    ast[AST_LOGP] = (float)lpm;
+  }
+}
+// Reinforce.update's policy loss (reinforce.py:52-61) for a categorical policy: reinforce_loss_kernel's record, ent = ent.mean().
+__global__ __launch_bounds__(1024) void reinforce_cat_loss_kernel(ActorArgs p, const UpdCtl* __restrict__ ctl,
+                                                                 float* __restrict__ rst_all) {
+  const int n = p.n;
+  const float amean = p.st[ST_ADV_MEAN], astd = p.st[ST_ADV_STD];
+  double s_lp = 0.0, s_lp2 = 0.0, s_loss = 0.0, s_ent = 0.0;
+  float lp_mx = -INFINITY, lp_mn = INFINITY;
+  int sat = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const CatLossRow o = cat_loss_row(p, i, amean, astd, sat);
+    s_loss += (double)(-o.lp * o.an);
+    s_lp += o.lp; s_lp2 += (double)o.lp * o.lp;
+    lp_mx = fmaxf(lp_mx, o.lp); lp_mn = fminf(lp_mn, o.lp);
+    s_ent += o.ent;
+  }
+  const Red4 r = block_red4(s_lp, s_lp2, lp_mx, lp_mn);
+  const Red4 r2 = block_red4(s_loss, (double)sat, 0.f, 0.f);
+  const Red4 r3 = block_red4(s_ent, 0.0, 0.f, 0.f);
+  if (threadIdx.x == 0) {
+    float* st = p.st;
+    const double dn = (double)n;
+    const double lpm = r.s / dn, entm = r3.s / dn;
+    const float loss = (float)(r2.s / dn - (double)p.ent_coef * entm);
+    const float lps = (float)sqrt(fmax(0.0, (r.s2 - dn * lpm * lpm) / (dn - 1.0)));  // (n >= 2: never one element)
+    st[ST_PI_LOSS] = loss;
+    st[ST_LP_MEAN] = (float)lpm;
+    st[ST_LP_STD] = lps;
+    st[ST_LP_MAX] = r.mx; st[ST_LP_MIN] = r.mn;
+    if (p.gscale != 1.f) st[ST_F16_SAT] += (float)r2.s2;
+    float* rst = rst_all + (int64_t)ctl->upd_index * RST_SIZE;
+    // advs/std: numpy's (population) std of the host batch, as in reinforce_loss_kernel
+    rst[RST_ADV_MEAN] = st[ST_ADV_MEAN]; rst[RST_ADV_STD] = (float)sqrt((double)st[ST_ADV_M2] / dn);
+    rst[RST_ADV_MAX] = st[ST_ADV_MAX]; rst[RST_ADV_MIN] = st[ST_ADV_MIN];
+    rst[RST_PI_LOSS] = loss;
+    rst[RST_ENT] = (float)entm;
     rst[RST_LP_MEAN] = (float)lpm;
     rst[RST_LP_STD] = lps;
     rst[RST_LP_MAX] = r.mx; rst[RST_LP_MIN] = r.mn;

@@ -129,7 +129,13 @@ struct v4l_net {
   // GaussianContPolicy (continuous_policy.py:222-236): the head's last layer is [mean | raw log sigma], out_dim = 2 A columns
   bool sd() const { return cfg.has_logstd == V4L_LOGSTD_HEAD; }
   // action dimensions A of a policy: the head's width, or half of it where the other half is the per-row log sigma
-  int act_dim() const { return sd() ? cfg.out_dim / 2 : cfg.out_dim; }
+  // CategoricalDisPolicy (policies/discrete_policies.py:127-172; v4l_net_set_categorical): a has_logstd = 0 state-MLP net whose
+  // K = out_dim head columns are the logits of a policy over K actions. Not a cfg field: v4l_net_cfg is frozen
+  bool categorical = false;
+  bool cat() const { return categorical; }
+  // true for every net a trainer / an actor takes as its policy
+  bool is_policy() const { return cfg.has_logstd != V4L_LOGSTD_NONE || categorical; }
+  int act_dim() const { return cat() ? 1 : sd() ? cfg.out_dim / 2 : cfg.out_dim; }
   std::vector<v4l::ParamInfo> params;
   int64_t total_params = 0;
   // layers

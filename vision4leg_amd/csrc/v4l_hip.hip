@@ -2271,7 +2271,9 @@ enum class StepRoute {
 static StepRoute step_route(const v4l_actor* a, int shared_encoder) {
   const v4l_net *pf = a->pf, *vf = a->vf;
   const v4l_net_cfg &p = pf->cfg, &v = vf->cfg;
-  if (!shared_encoder) return StepRoute::GENERAL;
+  // (a categorical policy, v4l_net_set_categorical: always layer by layer + act_finish_cat_kernel — the fused state-MLP kernels'
+  // epilogues are Gaussian — also where a shared trunk, REINFORCE's zero_critic, would pick one of them)
+  if (!shared_encoder || pf->cat()) return StepRoute::GENERAL;
   auto both = [&](auto ok) { return ok(p) && ok(v); };
   auto frag_heads = [&] { return pf->head[0].pkf >= 0 && vf->head[0].pkf >= 0; };  // fragment-order packs of the heads
   // tanh_action policies (TanhNormal): the fused kernels' epilogues sample through tanh like act_finish_kernel (round 5), except
@@ -2678,6 +2680,12 @@ static int launch_rec_loss(const char* label, const RecLossKernel (&family)[4], 
   V4L_LAUNCH_CHECK();
   return 0;
 }
+// the same launch for a categorical policy (v4l_net_set_categorical): one instantiation per learner
+static int launch_cat_loss(const char* label, RecLossKernel kern, hipStream_t s, const ActorArgs& aa, const UpdCtl* ctl, float* rec_all) {
+  V4L_KLAUNCH(label, 0, s, kern, dim3(1), loss_block(aa.n), 0, s, aa, ctl, rec_all);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
 
 // Captures what body() launches on s (thread-local mode) and instantiates it into *exec. A failed body ends the capture,
 // destroys what was recorded and returns the body's rc; otherwise the end-capture error decides.
@@ -2706,7 +2714,9 @@ const char* v4l_last_error(void) { return v4l::last_error(); }
 // actor_loss_sd_kernel, the per-row sampling epilogues of rollout_mlp_kernel / act_finish_sd_kernel, v4l_gauss_head_sd
 // 114: REINFORCE on every net kind the PPO update takes: v4l_trainer_reinforce_actor_grads / _update_next / _update_run / _graph_counts,
 // V4L_REINFORCE_STATS (reinforce_loss_kernel; the opening launch packs the policy)
-int v4l_version(void) { return 114; }  // 112: A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
+// 115: v4l_net_set_categorical (CategoricalDisPolicy, policies/discrete_policies.py:127-172: K = out_dim logits, one action index) — v4l_cat_head,
+// v4l_cat_sample, a2c_cat_loss_kernel / reinforce_cat_loss_kernel behind the A2C and REINFORCE entry points, act_finish_cat_kernel on the GENERAL step
+int v4l_version(void) { return 115; }  // 112: A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
 int v4l_abi_sizeof(int which) {
   return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) :
          which == 4 ? (int)sizeof(v4l_vmpo_hyper) : -1;  // (3 stays unassigned)
@@ -2719,6 +2729,18 @@ int v4l_net_create(const v4l_net_cfg* cfg, v4l_net** out) {
   int rc = n->build();
   if (rc) { delete n; return rc; }
   *out = n;
+  return 0;
+}
+int v4l_net_set_categorical(v4l_net* net, int on) {
+  V4L_REQUIRE(net != nullptr, "v4l_net_set_categorical: null argument");
+  V4L_REQUIRE(!net->bound, "v4l_net_set_categorical: the net is bound already (set the flag between v4l_net_create and v4l_net_bind)");
+  V4L_REQUIRE(net->cfg.kind == V4L_NET_MLP, "v4l_net_set_categorical: a categorical policy is a state-MLP net (V4L_NET_MLP, the "
+              "reference's networks.Net), got kind %d", net->cfg.kind);
+  V4L_REQUIRE(net->cfg.has_logstd == V4L_LOGSTD_NONE, "v4l_net_set_categorical: has_logstd must be 0 (V4L_LOGSTD_NONE: a categorical "
+              "policy has no log sigma), got %d", net->cfg.has_logstd);
+  V4L_REQUIRE(net->cfg.out_dim >= 2 && net->cfg.out_dim <= V4L_OUT_LD, "v4l_net_set_categorical: 2 <= out_dim <= %d (V4L_OUT_LD: the "
+              "logits of the K actions fill one padded head row) required, got %d", V4L_OUT_LD, net->cfg.out_dim);
+  net->categorical = on != 0;
   return 0;
 }
 void v4l_net_destroy(v4l_net* net) {
@@ -2956,6 +2978,25 @@ int v4l_gauss_head_sd(const float* out_dev, const float* acts_dev, const float* 
   V4L_LAUNCH_CHECK();
   return 0;
 }
+int v4l_cat_head(const float* logits_dev, const float* acts_dev, int n, int K, float* probs_dev, float* ent_dev, float* logp_dev,
+                 void* stream) {
+  V4L_REQUIRE(logits_dev && probs_dev && ent_dev && n > 0, "v4l_cat_head: bad argument");
+  V4L_REQUIRE(K >= 2 && K <= V4L_OUT_LD, "v4l_cat_head: 2<=K<=%d (V4L_OUT_LD) required, got %d", V4L_OUT_LD, K);
+  V4L_REQUIRE(acts_dev == nullptr || logp_dev != nullptr, "v4l_cat_head: logp_dev is null");
+  hipLaunchKernelGGL(cat_head_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, logits_dev, acts_dev, n, K, probs_dev,
+                     ent_dev, logp_dev);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
+int v4l_cat_sample(const float* probs_dev, const float* u_dev, int n, int K, int deterministic, int64_t* idx_dev, void* stream) {
+  V4L_REQUIRE(probs_dev && idx_dev && n > 0, "v4l_cat_sample: bad argument");
+  V4L_REQUIRE(deterministic || u_dev != nullptr, "v4l_cat_sample: u_dev is null");
+  V4L_REQUIRE(K >= 2 && K <= V4L_OUT_LD, "v4l_cat_sample: 2<=K<=%d (V4L_OUT_LD) required, got %d", V4L_OUT_LD, K);
+  hipLaunchKernelGGL(cat_sample_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, probs_dev, u_dev, n, K,
+                     deterministic ? 1 : 0, (long long*)idx_dev);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
 int v4l_col0(const float* src_dev, int n, float* dst_dev, void* stream) {
   V4L_REQUIRE(src_dev && dst_dev && n > 0, "v4l_col0: bad argument");
   hipLaunchKernelGGL(col0_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, src_dev, n, dst_dev);
@@ -3077,7 +3118,8 @@ int64_t v4l_prof_collect(char* buf, int64_t cap) {
 // ------------------------------------------------------------------------------------------ actor (rollout step)
 int v4l_actor_create(v4l_net* pf, v4l_net* vf, int E, v4l_actor** out) {
   V4L_REQUIRE(pf && vf && out && E > 0, "v4l_actor_create: bad argument");
-  V4L_REQUIRE(pf->cfg.has_logstd && !vf->cfg.has_logstd && vf->cfg.out_dim == 1 && pf->cfg.kind == vf->cfg.kind &&
+  // (a policy: Gaussian, or a net flagged by v4l_net_set_categorical)
+  V4L_REQUIRE(pf->is_policy() && !vf->is_policy() && vf->cfg.out_dim == 1 && pf->cfg.kind == vf->cfg.kind &&
                   pf->cfg.compute == vf->cfg.compute && pf->cfg.state_dim == vf->cfg.state_dim &&
                   pf->cfg.n_enc_hidden == vf->cfg.n_enc_hidden && pf->cfg.activation == vf->cfg.activation,
               "v4l_actor_create: pf must be a Gaussian policy and vf a value net of the same kind/compute/shape/activation");
@@ -3235,7 +3277,11 @@ static int run_actor_step(v4l_actor* a, const StepIO& io, int shared_encoder, hi
     if ((rc = fwd(vf, ws_vf, s, nullptr, 0))) return rc;
   }
   g_op = "sample";
-  if (pf->sd())
+  if (pf->cat())  // io.eps: [E] uniforms (negative: argmax); io.mean / io.stdv are not written
+    V4L_KLAUNCH("act_finish", 0, s, act_finish_cat_kernel, dim3(1), dim3(256), 0, s, a->ctl, ws_pf + pf->layout(E).out,
+                ws_vf + vf->layout(E).out, io.eps, E, pf->cfg.out_dim, io.acts_roll, io.values_roll, io.logp_roll, io.action, io.ent,
+                io.value);
+  else if (pf->sd())
     V4L_KLAUNCH("act_finish", 0, s, act_finish_sd_kernel, dim3(1), dim3(256), 0, s, a->ctl, ws_pf + pf->layout(E).out,
                 ws_vf + vf->layout(E).out, io.eps, E, pf->act_dim(), io.acts_roll, io.values_roll, io.logp_roll, io.action, io.mean,
                 io.stdv, io.ent, io.value, pf->cfg.tanh_action);
@@ -3375,7 +3421,9 @@ int v4l_actor_step_rows(v4l_actor* a, const double* rows_host, int64_t ld, float
 int v4l_trainer_create(v4l_net* pf, v4l_net* vf, v4l_net* target_pf, v4l_trainer** out) {
   V4L_REQUIRE(pf && vf && target_pf && out, "v4l_trainer_create: null argument");
   // (a policy / target pair with a logstd parameter each, or V4L_LOGSTD_HEAD each: GaussianContPolicy, continuous_policy.py:222-236)
-  V4L_REQUIRE(pf->cfg.has_logstd && pf->cfg.has_logstd == target_pf->cfg.has_logstd && !vf->cfg.has_logstd && vf->cfg.out_dim == 1,
+  // or flagged by v4l_net_set_categorical each (CategoricalDisPolicy, policies/discrete_policies.py:127-172)
+  V4L_REQUIRE(pf->is_policy() && pf->cfg.has_logstd == target_pf->cfg.has_logstd && pf->cat() == target_pf->cat() &&
+                  !vf->is_policy() && vf->cfg.out_dim == 1,
               "v4l_trainer_create: pf/target_pf must be Gaussian policies of one kind (a logstd parameter each, or "
               "V4L_LOGSTD_HEAD each) and vf a scalar value net");
   V4L_REQUIRE(pf->cfg.out_dim == target_pf->cfg.out_dim, "v4l_trainer_create: pf and target_pf disagree on out_dim");
@@ -3551,10 +3599,11 @@ static ActorArgs actor_args(const v4l_trainer* tr, const v4l_rollout* ro, int ro
   const Layout Lp = pf->layout(rows);
   ActorArgs aa;
   memset(&aa, 0, sizeof(aa));
-  aa.mean = tr->ws + Lp.out; aa.logstd = pf->p[pf->logstd];
+  // (a categorical policy: mean = the logits rows, A = K, no log sigma)
+  aa.mean = tr->ws + Lp.out; aa.logstd = pf->cat() ? nullptr : pf->p[pf->logstd];
   aa.acts = ro->acts_dev; aa.adv = ro->advs_dev; aa.rowidx = rowidx;
   aa.n = rows; aa.A = pf->cfg.out_dim; aa.inv_n = 1.f / (float)rows;
-  aa.dmean = tr->ws + Lp.dout; aa.dlogstd = tr->g_pf + pf->params[pf->logstd].goff; aa.st = tr->stats_cur;
+  aa.dmean = tr->ws + Lp.dout; aa.dlogstd = pf->cat() ? nullptr : tr->g_pf + pf->params[pf->logstd].goff; aa.st = tr->stats_cur;
   aa.tanh_action = pf->cfg.tanh_action;
   aa.gscale = v4l_net_grad_scale(pf, rows);
   return aa;
@@ -3679,6 +3728,8 @@ int v4l_trainer_critic_step(v4l_trainer* tr, const v4l_ppo_hyper* hp, void* stre
 int v4l_trainer_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, void* stream) {
   int rc = check_update_args(tr, ro, n, hp);
   if (rc) return rc;
+  V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_actor_grads: a categorical policy (v4l_net_set_categorical) runs under the A2C and REINFORCE updates only: the PPO "
+              "loss kernels are Gaussian");
   hipStream_t s = (hipStream_t)stream;
   v4l_net *pf = tr->pf, *tp = tr->tpf;
   float* st = tr->stats_cur;
@@ -3826,6 +3877,8 @@ static int check_vmpo_args(const v4l_trainer* tr, const v4l_rollout* ro, int n, 
   if (rc) return rc;
   V4L_REQUIRE(!tr->pf->sd(), "v4l_trainer_vmpo: a V4L_LOGSTD_HEAD policy (GaussianContPolicy) runs under the PPO update only: the V-MPO "
               "loss kernel takes one log sigma per action column");
+  V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_vmpo: a categorical policy (v4l_net_set_categorical) runs under the A2C and REINFORCE updates "
+              "only: the V-MPO loss kernel and its KL are Gaussian");
   V4L_REQUIRE(tr->vmpo != nullptr, "v4l_trainer_vmpo_actor_grads: no V-MPO state (v4l_trainer_vmpo_init)");
   V4L_REQUIRE(n <= tr->vmpo_n_max, "v4l_trainer_vmpo_actor_grads: n = %d is over the V-MPO block's n_max = %d", n, tr->vmpo_n_max);
   V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_vmpo_actor_grads: V-MPO runs in a single process");
@@ -4047,6 +4100,8 @@ int v4l_trainer_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const
                             void* stream) {
   int rc = check_update_args(tr, ro, n, hp);
   if (rc) return rc;
+  V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_update_next: a categorical policy (v4l_net_set_categorical) runs under the A2C and REINFORCE updates only: the PPO "
+              "loss kernels are Gaussian");
   hipStream_t s = (hipStream_t)stream;
   drop_vmpo_graph(tr);  // (a PPO update on a V-MPO trainer runs the policy's pass over n rows: other descriptor tables)
   drop_a2c_graph(tr);
@@ -4074,6 +4129,8 @@ int v4l_trainer_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const 
                            void* stream) {
   int rc = check_update_args(tr, ro, n, hp);
   if (rc) return rc;
+  V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_update_run: a categorical policy (v4l_net_set_categorical) runs under the A2C and REINFORCE updates only: the PPO "
+              "loss kernels are Gaussian");
   V4L_REQUIRE(count >= 1, "v4l_trainer_update_run: count must be >= 1");
   hipStream_t s = (hipStream_t)stream;
   GraphKey key;
@@ -4243,7 +4300,9 @@ static int a2c_actor_stage(v4l_trainer* tr, const v4l_rollout* ro, int n, const 
   g_op = "loss";
   ActorArgs aa = actor_args(tr, ro, n, rowidx);
   aa.ent_coef = hp->entropy_coeff;
-  if ((rc = launch_rec_loss("a2c_loss", V4L_LOSS_FAMILY(a2c_loss_kernel), s, aa, tr->ctl, astats_all_dev))) return rc;
+  if (pf->cat()) {
+    if ((rc = launch_cat_loss("a2c_loss", a2c_cat_loss_kernel, s, aa, tr->ctl, astats_all_dev))) return rc;
+  } else if ((rc = launch_rec_loss("a2c_loss", V4L_LOSS_FAMILY(a2c_loss_kernel), s, aa, tr->ctl, astats_all_dev))) return rc;
   PhaseScope ps("pf.bwd");
   return v4l_net_backward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, tr->g_pf, stream);
 }
@@ -4408,7 +4467,9 @@ static int reinforce_actor_stage(v4l_trainer* tr, const v4l_rollout* ro, int n, 
   g_op = "loss";
   ActorArgs aa = actor_args(tr, ro, n, rowidx);
   aa.ent_coef = hp->entropy_coeff;
-  if ((rc = launch_rec_loss("reinforce_loss", V4L_LOSS_FAMILY(reinforce_loss_kernel), s, aa, tr->ctl, rstats_all_dev))) return rc;
+  if (pf->cat()) {
+    if ((rc = launch_cat_loss("reinforce_loss", reinforce_cat_loss_kernel, s, aa, tr->ctl, rstats_all_dev))) return rc;
+  } else if ((rc = launch_rec_loss("reinforce_loss", V4L_LOSS_FAMILY(reinforce_loss_kernel), s, aa, tr->ctl, rstats_all_dev))) return rc;
   PhaseScope ps("pf.bwd");
   return v4l_net_backward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, tr->g_pf, stream);
 }

@@ -101,19 +101,23 @@ def _require_gpu(t, what):
 class HipNet:
   """One v4l_net plan bound to the parameters of a top-level module (state_dict keys = reference names)."""
 
-  def __init__(self, module, cfg):
+  def __init__(self, module, cfg, categorical=False):
     self.module = module
     self.cfg = cfg
     self.L = _lib.lib()
     h = C.c_void_p()
     check(self.L.v4l_net_create(C.byref(cfg), C.byref(h)), "v4l_net_create")
     self.h = h
+    # CategoricalDisPolicy (discrete_policies.py:127-172): the head row holds K = out_dim logits, an action is one index
+    self.categorical = bool(categorical)
+    if self.categorical:
+      check(self.L.v4l_net_set_categorical(h, 1), "v4l_net_set_categorical")
     self.kind = cfg.kind
     self.compute = cfg.compute
     self.out_dim = cfg.out_dim
     # GaussianContPolicy (continuous_policy.py:222-236): the head row is [mean | raw log sigma]; act_dim is A, out_dim the row's width
     self.logstd_head = cfg.has_logstd == _lib.V4L_LOGSTD_HEAD
-    self.act_dim = cfg.out_dim // 2 if self.logstd_head else cfg.out_dim
+    self.act_dim = 1 if self.categorical else cfg.out_dim // 2 if self.logstd_head else cfg.out_dim
     self.state_dim = cfg.state_dim
     self.img_elems = 0 if cfg.kind == V4L_NET_MLP else cfg.in_channels * cfg.img_hw * cfg.img_hw
     self.Sp = self.L.v4l_net_state_ld(h)
@@ -350,6 +354,39 @@ class HipNet:
       check(self.L.v4l_gauss_head(_ptr(out), _ptr(logstd), _ptr(acts), n, A, _ptr(mean), _ptr(std), _ptr(lsc),
                                   _ptr(ent), _ptr(logp), _stream()), "v4l_gauss_head")
     return mean, std, lsc, ent.view(n, 1), (logp.view(n, 1) if logp is not None else None)
+
+
+  def categorical_dist(self, obs, acts=None):
+    """Categorical policy head: probs [n][K], ent [n] and log_prob [n] of the action indices acts (optional)."""
+    st, im, n = self.stage(obs)
+    out = self.forward(st, im, n)
+    return self.cat_head(out, n, acts)
+
+  def cat_head(self, out, n, acts=None):
+    """v4l_cat_head on padded logits rows [n][V4L_OUT_LD]: -> probs [n][K], ent [n], log_prob [n] | None."""
+    K, dev = self.out_dim, out.device
+    probs = torch.empty(n, K, dtype=torch.float32, device=dev)
+    ent = torch.empty(n, dtype=torch.float32, device=dev)
+    logp = None
+    if acts is not None:
+      acts = acts.reshape(n).contiguous().float()
+      logp = torch.empty(n, dtype=torch.float32, device=dev)
+    check(self.L.v4l_cat_head(_ptr(out), _ptr(acts), n, K, _ptr(probs), _ptr(ent), _ptr(logp), _stream()), "v4l_cat_head")
+    return probs, ent, logp
+
+
+def cat_sample(probs, u=None, deterministic=False):
+  """v4l_cat_sample: int64 [n] inverse-CDF indices of the uniforms u [n] under the rows of probs [n][K] (float32 device tensors), or
+  each row's first argmax (deterministic=True, u unused)."""
+  _require_gpu(probs, "probability rows")
+  probs = probs.contiguous().float()
+  n, K = probs.shape
+  if not deterministic:
+    u = u.reshape(n).contiguous().float()
+  idx = torch.empty(n, dtype=torch.int64, device=probs.device)
+  check(_lib.lib().v4l_cat_sample(_ptr(probs), _ptr(None if deterministic else u), n, K, int(bool(deterministic)), _ptr(idx),
+                                  _stream()), "v4l_cat_sample")
+  return idx
 
 
 class HipTrainer:
@@ -739,6 +776,13 @@ class HipActor:
     self.ctl = _buf(self.L.v4l_actor_ctl_bytes(h), torch.uint8, dev, zero=True)
     self.obs = torch.zeros(E, pf_net.state_dim + pf_net.img_elems, dtype=torch.float32, device=dev)
     self.eps = torch.zeros(E, A, dtype=torch.float32, device=dev)
+    # what the step's `eps` argument carries: [E][A] standard normals, zeros for a deterministic step; for a categorical policy
+    # [E][1] uniforms in [0, 1) (torch.rand on the current generator: the draw CategoricalDisPolicy.explore makes), -1 for the
+    # argmax. Bound once: _draw(buf) fills a noise buffer, _no_draw() sets self.eps for a deterministic step
+    if pf_net.categorical:
+      self._draw, self._no_draw = torch.Tensor.uniform_, (lambda eps=self.eps: eps.fill_(-1.0))
+    else:
+      self._draw, self._no_draw = torch.Tensor.normal_, self.eps.zero_
     z = lambda *shape: _buf(int(np.prod(shape)), torch.float32, dev, zero=True).view(*shape)
     self.action, self.mean, self.std, self.ent, self.value = z(E, A), z(E, A), z(E, A), z(E, 1), z(E, 1)
     self.shared_encoder, self.graph = bool(shared_encoder), bool(graph)
@@ -770,6 +814,8 @@ class HipActor:
                   _ptr(self.mean), _ptr(self.std), _ptr(self.ent), _ptr(self.value), int(self.shared_encoder),
                   int(self.graph))
     self._out = {"action": self.action, "mean": self.mean, "std": self.std, "ent": self.ent, "value": self.value}
+    if self.pf.categorical:  # the step writes neither mean nor std (v4l_net_set_categorical); the action is [E][1] indices
+      del self._out["mean"], self._out["std"]
 
   def seek(self, t):
     check(self.L.v4l_actor_seek(self.h, int(t), _stream()), "v4l_actor_seek")
@@ -809,7 +855,7 @@ class HipActor:
     E, A = self.eps.shape
     if getattr(self, "_bulk_buf", None) is None or self._bulk_buf.shape[0] != n_steps:
       self._bulk_buf = torch.empty(n_steps, E, A, dtype=torch.float32, device=self.device)
-    self._bulk_buf.normal_()
+    self._draw(self._bulk_buf)
     self._bulk, self._bulk_t = self._bulk_buf, 0
 
   def step(self, obs, deterministic=False):
@@ -853,10 +899,10 @@ class HipActor:
       if self._bulk_t >= bulk.shape[0]:
         self._bulk = None
     elif not deterministic:
-      self.eps.normal_()
+      self._draw(self.eps)
       self._eps_zero = False
     elif not getattr(self, "_eps_zero", False):
-      self.eps.zero_()
+      self._no_draw()
       self._eps_zero = True
     if self.own:
       self.seek(0)
@@ -952,10 +998,10 @@ class HipActor:
       if self._bulk_t >= bulk.shape[0]:
         self._bulk = None
     elif not deterministic:
-      self.eps.normal_()
+      self._draw(self.eps)
       self._eps_zero = False
     elif not getattr(self, "_eps_zero", False):
-      self.eps.zero_()
+      self._no_draw()
       self._eps_zero = True
     if self.own:
       self.seek(0)
@@ -1001,10 +1047,10 @@ class HipActor:
       if self._bulk_t >= bulk.shape[0]:
         self._bulk = None
     elif not deterministic:
-      self.eps.normal_()
+      self._draw(self.eps)
       self._eps_zero = False
     elif not getattr(self, "_eps_zero", False):
-      self.eps.zero_()
+      self._no_draw()
       self._eps_zero = True
     if self.own:
       self.seek(0)
@@ -1040,10 +1086,10 @@ class HipActor:
       if self._bulk_t >= bulk.shape[0]:
         self._bulk = None
     elif not deterministic:
-      self.eps.normal_()  # torch's generator: the same standard-normal draws Normal(mean, std).sample() would use
+      self._draw(self.eps)  # torch's generator: the same standard-normal draws Normal(mean, std).sample() would use
       self._eps_zero = False
     elif not getattr(self, "_eps_zero", False):
-      self.eps.zero_()  # action = mean + std * 0
+      self._no_draw()  # action = mean + std * 0
       self._eps_zero = True
     if self.own:
       self.seek(0)

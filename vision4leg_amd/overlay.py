@@ -12,6 +12,7 @@ stays the reference's, so `starter/ppo_*.py` runs unchanged:
     overlay.install(a2c=True)         # + `torchrl.algo.A2C` on the HIP engine, state-MLP nets only (opt-in, like vmpo)
     overlay.install(reinforce=True)   # + `torchrl.algo.Reinforce` on the HIP engine, `networks.ZeroNet` -> this package's (opt-in)
     overlay.install(state_std=True)   # + `torchrl.policies.GaussianContPolicy` (log-std from the head) on the HIP engine (opt-in)
+    overlay.install(discrete=True)    # + `torchrl.policies.CategoricalDisPolicy` (discrete actions, under A2C / Reinforce) (opt-in)
 
 Rebinding is by name on every already-imported `torchrl.<pkg>` module that defines the name (the package and the
 sub-module that holds the class: `from torchrl.algo import PPO`, `from torchrl.algo.on_policy.ppo import PPO` and
@@ -66,6 +67,11 @@ STATE_STD_NAMES = {
     "policies": ["GaussianContPolicy"],
 }
 
+# discrete=True: the categorical policy over K discrete actions (discrete_policies.py:127-172), state-MLP nets under A2C / Reinforce
+DISCRETE_NAMES = {
+    "policies": ["CategoricalDisPolicy"],
+}
+
 _installed = {}
 
 
@@ -83,13 +89,14 @@ def _rebind(ref_pkg_name, name, obj, always_on_package=False):
     return hits
 
 
-def install(fast_path=False, reference_package="torchrl", vmpo=False, a2c=False, state_std=False, reinforce=False):
+def install(fast_path=False, reference_package="torchrl", vmpo=False, a2c=False, state_std=False, reinforce=False, discrete=False):
     """Rebind the hot-path classes on the reference's `torchrl`. Returns {"pkg.name": [modules patched]}.
     vmpo=True also rebinds `torchrl.algo.VMPO` (vision4leg_amd.torchrl.algo.VMPO); without it VMPO stays the reference's.
     a2c=True also rebinds `torchrl.algo.A2C` (and nothing else); without it A2C stays the reference's.
     reinforce=True also rebinds `torchrl.algo.Reinforce` and `torchrl.networks.ZeroNet` (the report gains "algo.Reinforce" only);
     without it both stay the reference's.
-    state_std=True also rebinds `torchrl.policies.GaussianContPolicy` (and nothing else); without it that class stays the reference's."""
+    state_std=True also rebinds `torchrl.policies.GaussianContPolicy` (and nothing else); without it that class stays the reference's.
+    discrete=True also rebinds `torchrl.policies.CategoricalDisPolicy` (and nothing else); without it that class stays the reference's."""
     ref = importlib.import_module(reference_package)
     if getattr(ref, "__v4l_shell__", False):
         raise RuntimeError("vision4leg_amd.overlay: `%s` resolves to the HIP shell itself; put the reference "
@@ -122,7 +129,8 @@ def install(fast_path=False, reference_package="torchrl", vmpo=False, a2c=False,
             for name in names:
                 if not _rebind(ref_name, name, getattr(shell, name)):
                     raise RuntimeError("vision4leg_amd.overlay: the reference has no %s.%s to replace" % (ref_name, name))
-    for wanted, table in ((vmpo, VMPO_NAMES), (a2c, A2C_NAMES), (state_std, STATE_STD_NAMES), (reinforce, REINFORCE_NAMES)):
+    for wanted, table in ((vmpo, VMPO_NAMES), (a2c, A2C_NAMES), (state_std, STATE_STD_NAMES), (reinforce, REINFORCE_NAMES),
+                          (discrete, DISCRETE_NAMES)):
         if not wanted:
             continue
         for pkg, names in table.items():

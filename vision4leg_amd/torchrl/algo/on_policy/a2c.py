@@ -31,6 +31,7 @@ class A2C(_SecondRecordPPO):
     _passes = 1  # on_rl_algo.py:36-41
     _syncs_target = False
     _run_entry, _next_entry = "a2c_update_run", "a2c_update_next"
+    _takes_categorical = True  # policies.CategoricalDisPolicy: a2c_cat_loss_kernel in a2c_loss_kernel's place
 
     def __init__(self, pf, vf, plr=3e-4, vlr=3e-4, optimizer_class=optim.Adam, entropy_coeff=0.001, shuffle=True, tau=None, gae=True,
                  **kwargs):
@@ -64,5 +65,9 @@ class A2C(_SecondRecordPPO):
             net.to(device)
 
     def _info(self, row, arow):
-        """The logger's info dict of one update: the reference's 12 keys in its order (a2c.py:89-105), the A2C record's first."""
-        return {k: float(arow[j]) for j, k in enumerate(_lib.A2C_INFO_KEYS)}
+        """The logger's info dict of one update: the reference's 12 keys in its order (a2c.py:89-105), the A2C record's first —
+        8 for a categorical policy: the reference logs std/* only `if 'std' in out` (a2c.py:63-65,97-102)."""
+        info = {k: float(arow[j]) for j, k in enumerate(_lib.A2C_INFO_KEYS)}
+        if getattr(getattr(self, "pf", None), "categorical_head", False):
+            info = {k: info[k] for k in _lib.A2C_CAT_INFO_KEYS}
+        return info

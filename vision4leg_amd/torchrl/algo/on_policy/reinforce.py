@@ -32,6 +32,7 @@ class Reinforce(_SecondRecordPPO):
     _syncs_target = False
     _run_entry, _next_entry = "reinforce_update_run", "reinforce_update_next"
     _call_eps = None  # optimizer_class(params, lr=plr): torch's own eps, 1e-8 (reinforce.py:26-29)
+    _takes_categorical = True  # policies.CategoricalDisPolicy: reinforce_cat_loss_kernel in reinforce_loss_kernel's place
 
     def __init__(self, pf, plr, optimizer_class=optim.Adam, entropy_coeff=0.001, **kwargs):
         self._refuse(pf, kwargs)

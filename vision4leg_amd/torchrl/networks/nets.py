@@ -61,7 +61,8 @@ class _HipNetMixin:
                 raise NotImplementedError("vision4leg_amd: at most %d action dimensions (output_shape) are supported on the "
                                           "HIP engine (got %d)" % (_lib.V4L_MAX_ACT, cfg.out_dim))
             cfg.tanh_action = int(bool(getattr(self, "tanh_action", False)))  # Gaussian policies (continuous_policy.py)
-            self.__dict__["_hip"] = HipNet(self, cfg)
+            # policies.CategoricalDisPolicy: the flag of v4l_net_set_categorical (no field of the frozen v4l_net_cfg)
+            self.__dict__["_hip"] = HipNet(self, cfg, categorical=bool(getattr(self, "categorical_head", False)))
         return self.__dict__["_hip"]
 
     def mark_params_changed(self):
