@@ -410,6 +410,31 @@ int v4l_trainer_begin_guarded(v4l_trainer* tr, const int* rowidx_all_dev, float*
 /* The Adam step counts committed on the device so far (after a guarded run they may lag the number of updates, and differ
  * from each other). Synchronises the stream. */
 int v4l_trainer_steps(v4l_trainer* tr, int64_t* step_pf_out, int64_t* step_vf_out, void* stream);
+/* (version 116) The opt-in KL early stop of a run of PPO updates (PPO(target_kl=...)). v4l_trainer_kl_stop arms the run just
+ * opened by v4l_trainer_begin / _begin_guarded — call it after that call, for every run: it clears the latch on `stream` — or,
+ * with kl_all_dev = NULL, disarms the trainer (target_kl is then ignored). kl_all_dev: float [U][2]. The updates of an armed run go
+ * through v4l_trainer_kl_update_next / _update_run, which follow v4l_trainer_update_next / _update_run's rules (first update of a
+ * configuration eagerly, then single-update replays, from the next call on ONE hipGraph replay per run; use_graph captures on
+ * `stream` itself and refuses a caller's capture) with a graph key (PPO's fields + the KL array) and handles of their own:
+ * v4l_trainer_update, _update_next, _update_run and the staged calls neither read the setting nor change with it. An armed update
+ * is PPO's update plus one single-block launch (kl_stop_kernel) behind the policy's backward, in front of its clip + Adam launch:
+ *   approx_kl[u] = mean_i(log pi_old(a_i|s_i)) - mean_i(log pi_theta(a_i|s_i))     over the update's n rows, in double
+ * (Spinning Up's (logp_old - logp).mean(); the second mean is record slot 7, the first the mean of the log pi_old values the
+ * ratio used: ro->logp_old_dev, or the frozen target's log-probability of the stored actions). It writes
+ *   kl_all_dev[u][0] = approx_kl[u],   kl_all_dev[u][1] = 1.0 if the latch is set after this update's decision, else 0.0
+ * and sets the latch when approx_kl[u] > 1.5 * target_kl (a NaN does not latch: that is the guard's business). Once set, the latch
+ * stays set for the rest of the run, and every later clip + Adam launch of the run (clip_adam_kernel<WD, true>) skips exactly as a
+ * guarded non-finite step does: no write to parameters or moments, that optimiser's step count does not advance (read them with
+ * v4l_trainer_steps). The policy's step of the update that set the latch is the first one skipped. ONE DEVIATION from the
+ * single-loss implementations, which stop before any step of that minibatch: that update's critic step has already been taken,
+ * because the critic goes first (ppo.py:150-151). The guard's skip_all flags keep meaning "non-finite" only. The launch sequence
+ * of an update does not depend on the latch (a captured run stays one static graph: a stop saves no GPU time there). Single
+ * process only (no communicator, world_size 1); the V-MPO, A2C and REINFORCE entry points refuse an armed trainer. */
+int v4l_trainer_kl_stop(v4l_trainer* tr, double target_kl, float* kl_all_dev, void* stream);
+int v4l_trainer_kl_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, int use_graph, void* stream);
+int v4l_trainer_kl_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, int count, int use_graph,
+                              void* stream);
+int v4l_trainer_kl_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays);
 /* The next minibatch update, == PPO.update (ppo.py:125-153). use_graph=1: the launch sequence (~20 kernels) is
  * captured once per (rollout pointers, n, hyper-parameters) as a hipGraph and replayed; needs a non-default stream.
  * The first update of a configuration always runs eagerly. */

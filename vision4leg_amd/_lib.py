@@ -164,6 +164,10 @@ _SIGS = {
   "v4l_trainer_begin": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_int64, C.POINTER(PPOHyper), _P]),
   "v4l_trainer_begin_guarded": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_int64, C.c_int64, C.POINTER(PPOHyper), _P]),
   "v4l_trainer_steps": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+  "v4l_trainer_kl_stop": (C.c_int, [_P, C.c_double, _P, _P]),
+  "v4l_trainer_kl_update_next": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), C.c_int, _P]),
+  "v4l_trainer_kl_update_run": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), C.c_int, C.c_int, _P]),
+  "v4l_trainer_kl_graph_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
   "v4l_trainer_update_next": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), C.c_int, _P]),
   "v4l_host_cast_rows": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, _P, C.c_int, C.c_int]),
   "v4l_host_cast_simd": (C.c_int, []),

@@ -988,6 +988,60 @@ __device__ __forceinline__ void actor_loss_sd_body(const ActorArgs& p) {
 }
 template <bool TANH>
 __global__ __launch_bounds__(1024) void actor_loss_sd_kernel(ActorArgs p) { actor_loss_sd_body<TANH>(p); }
+
+// The KL early stop of PPO(target_kl=...) (v4l_trainer_kl_stop). Runs after the actor's loss launch has completed
+// the record (behind the policy's backward) and before the actor's clip_adam_kernel. Single block, row-strided.
+//   approx_kl = mean_i(log pi_old(a_i|s_i)) - mean_i(log pi_theta(a_i|s_i))      ((logp_old - logp).mean(), Spinning Up's PPO)
+// The second mean is the record's ST_LP_MEAN, whichever loss route wrote it. The first is the mean of the log pi_old values the
+// ratio used: logp_old[slot] where the rollout stores it, otherwise the frozen target's log-probability of the stored action from
+// the target's head rows (tmean; log sigma from tlogstd, or sd: from columns A .. 2A-1 of the row) — the expressions of actor_row /
+// actor_loss_sd_body's lpo, spelled out again here on purpose (those kernels' row code stays where it is: DESIGN.md 7).
+// Sum and subtraction in double. kl_all[u] = {approx_kl, latch after this update's decision (1.0 / 0.0)}, u = UpdCtl::upd_index (the
+// closing clip_adam_kernel advances it after this launch). The latch (UpdCtl::kl_stop) is set when approx_kl > thresh
+// (= 1.5 * target_kl, formed by the host in double) and never cleared here; a NaN approx_kl compares false and does not latch.
+struct KlArgs {
+  const float *tmean, *tlogstd, *logp_old, *acts;  // tmean / tlogstd unused with a stored logp_old; tlogstd unused with sd
+  const int* rowidx;
+  int n, A, sd;
+  const float* st;   // the record being filled (ST_LP_MEAN)
+  const int* upd_index;  // &UpdCtl::upd_index of the open run
+  int* latch;            // &UpdCtl::kl_stop
+  float* kl_all;         // [U][2]
+  double thresh;
+};
+template <bool TANH>
+__global__ __launch_bounds__(1024) void kl_stop_kernel(KlArgs q) {
+  const int n = q.n, A = q.A;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int slot = q.rowidx ? q.rowidx[i] : i;
+    float lpo = 0.f;
+    if (q.logp_old != nullptr) {
+      lpo = q.logp_old[slot];
+    } else {
+      const float* __restrict__ trow = q.tmean + (int64_t)i * OUT_LD;
+      for (int a = 0; a < A; ++a) {
+        const float act = q.acts[(int64_t)slot * A + a];
+        const float x = TANH ? tanh_pre(act) : act;
+        const float corr = TANH ? tanh_corr(act) : 0.f;
+        const float tls = fminf(fmaxf(q.sd ? trow[A + a] : q.tlogstd[a], LOG_SIG_MIN), LOG_SIG_MAX);
+        const float tsg = expf(tls), tlsg = logf(tsg);
+        const float dt = x - trow[a];
+        lpo += -(dt * dt) / (2.f * tsg * tsg) - tlsg - HALF_LOG_2PI - corr;
+      }
+    }
+    s += (double)lpo;
+  }
+  const Red4 r = block_red4(s, 0.0, 0.f, 0.f);
+  if (threadIdx.x == 0) {
+    const double kl = r.s / (double)n - (double)q.st[ST_LP_MEAN];
+    const int u = *q.upd_index;
+    const int latch = (*q.latch != 0 || kl > q.thresh) ? 1 : 0;
+    *q.latch = latch;
+    q.kl_all[(int64_t)u * 2] = (float)kl;
+    q.kl_all[(int64_t)u * 2 + 1] = latch ? 1.f : 0.f;
+  }
+}
 #pragma clang fp contract(fast)
 
 // Gaussian head post-processing for the policy API (continuous_policy.py:85-146,486-492): from the padded
@@ -1119,6 +1173,8 @@ struct UpdCtl {
   float wd32;           // the same as torch hands it to grad.add(param, alpha=weight_decay) on fp32 tensors
   int decoupled;        // != 0: AdamW (decay the parameter), 0: L2 (decay joins the gradient)
   float decay[2];       // decoupled: 1 - lr * weight_decay per optimiser, formed in double and rounded once like step_size
+  int kl_stop;          // the KL early stop's latch: cleared by v4l_trainer_kl_stop when it arms a run (kl_arm_kernel), set by
+                        // kl_stop_kernel, read by clip_adam_kernel<WD, true> only — no other kernel touches the word
 };
 static_assert(sizeof(UpdCtl) <= 256, "UpdCtl must fit in front of stats_cur (control buffer layout [UpdCtl | stats_cur | rowidx_cur])");
 __global__ void ctl_set_kernel(UpdCtl* c, int upd_index, long long step_pf, long long step_vf, double lr_pf, double lr_vf, float b1,
@@ -1126,6 +1182,7 @@ __global__ void ctl_set_kernel(UpdCtl* c, int upd_index, long long step_pf, long
   c->upd_index = upd_index; c->step[0] = step_pf; c->step[1] = step_vf; c->lr_pf = lr_pf; c->lr_vf = lr_vf; c->beta1 = b1; c->beta2 = b2;
   c->weight_decay = weight_decay; c->wd32 = (float)weight_decay; c->decoupled = decoupled; c->decay[0] = 1.f; c->decay[1] = 1.f;
 }
+__global__ void kl_arm_kernel(UpdCtl* c) { c->kl_stop = 0; }
 // the candidate Adam step sizes / bias corrections of the update being opened, from the committed counts + 1 (double precision,
 // like torch/optim/adam.py::_single_tensor_adam). Nothing is committed here: block 0 of each optimiser's clip_adam_kernel
 // advances that optimiser's count when its step is taken.
@@ -1195,7 +1252,9 @@ __device__ __forceinline__ void upd_begin_body(UpdCtl* c, const int* __restrict_
 //   WD_DECOUPLED  torch.optim.AdamW: param.mul_(1 - lr * wd), then the plain step on the decayed parameter
 // The norm (and the logged grad_norm) is the raw gradient's either way: clip_grad_norm_ runs before optimizer.step().
 enum { WD_NONE = 0, WD_COUPLED = 1, WD_DECOUPLED = 2 };
-template <int WD>
+// KL: the launch belongs to a run with the KL early stop armed (v4l_trainer_kl_update_*). A template argument like WD, same
+// signature: the instantiation every other run launches, clip_adam_kernel<WD>, has neither the load nor the test.
+template <int WD, bool KL = false>
 __global__ __launch_bounds__(256) void clip_adam_kernel(const ParamSeg* __restrict__ segs, int nseg,
                                                         const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, const float* __restrict__ part, int npart,
@@ -1236,11 +1295,15 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const ParamSeg* __restri
   // skip_all != null (the opt-in guard): a step whose pre-clip norm is not finite writes nothing and does not count. Every block
   // summed the same partials in the same order, so every block takes the same decision without a grid-wide sync (data parallel:
   // the partials are those of the all-reduced bucket, so every rank skips the same steps).
-  const bool skip = skip_all != nullptr && !(fabsf(tot) <= 3.0e38f);
+  const bool nonfinite = skip_all != nullptr && !(fabsf(tot) <= 3.0e38f);
+  // KL: a set latch skips the step the same way. The latch was written by an earlier launch on this stream (kl_stop_kernel) and
+  // no launch writes it while this one runs: every block reads the same word.
+  bool skip = nonfinite;
+  if (KL) skip = skip || ctl->kl_stop != 0;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     if (!skip) ctl->step[which] = ctl->step[which] + 1;  // commit this optimiser's Adam step
     // (the update index before the closing block below advances it: program order of this thread)
-    if (skip_all != nullptr) skip_all[(int64_t)ctl->upd_index * 2 + which] = skip ? 1 : 0;
+    if (skip_all != nullptr) skip_all[(int64_t)ctl->upd_index * 2 + which] = nonfinite ? 1 : 0;  // "non-finite" only, never the KL stop
   }
   if (blockIdx.x == 0 && close_ctl != nullptr) {
     // last launch of an update: publish the statistics record (this block just completed it with the policy's gradient

@@ -289,4 +289,15 @@ struct v4l_trainer {
   int rexec_run_count = 0;
   bool rwarm = false;
   int64_t reinforce_captures = 0, reinforce_replays = 0;  // (v4l_trainer_reinforce_graph_counts)
+  // the KL early stop (v4l_trainer_kl_stop): [U][2] floats {approx_kl, latch} per update, null: disarmed; kl_thresh = 1.5 * target_kl.
+  // Armed updates run through entry points of their own (v4l_trainer_kl_update_next / _update_run) with a key (GraphKey + the KL
+  // array) and handles of their own; PPO's entry points and graphs are as they were
+  float* kl_all = nullptr;
+  double kl_thresh = 0.0;
+  A2cGraphKey kkey = {};
+  hipGraphExec_t kexec = nullptr;
+  hipGraphExec_t kexec_run = nullptr;
+  int kexec_run_count = 0;
+  bool kwarm = false;
+  int64_t kl_captures = 0, kl_replays = 0;
 };

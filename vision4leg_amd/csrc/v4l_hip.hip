@@ -2716,7 +2716,8 @@ const char* v4l_last_error(void) { return v4l::last_error(); }
 // V4L_REINFORCE_STATS (reinforce_loss_kernel; the opening launch packs the policy)
 // 115: v4l_net_set_categorical (CategoricalDisPolicy, policies/discrete_policies.py:127-172: K = out_dim logits, one action index) — v4l_cat_head,
 // v4l_cat_sample, a2c_cat_loss_kernel / reinforce_cat_loss_kernel behind the A2C and REINFORCE entry points, act_finish_cat_kernel on the GENERAL step
-int v4l_version(void) { return 115; }  // 112: A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
+// 116: the opt-in KL early stop inside a run of PPO updates: v4l_trainer_kl_stop, v4l_trainer_kl_update_next / _update_run / _graph_counts (kl_stop_kernel, clip_adam_kernel<WD, true>)
+int v4l_version(void) { return 116; }  // 112: A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
 int v4l_abi_sizeof(int which) {
   return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) :
          which == 4 ? (int)sizeof(v4l_vmpo_hyper) : -1;  // (3 stays unassigned)
@@ -3462,7 +3463,14 @@ static void drop_reinforce_graph(v4l_trainer* tr) {
   tr->rexec_run_count = 0;
   tr->rwarm = false;
 }
+static void drop_kl_graph(v4l_trainer* tr) {
+  if (tr->kexec) { (void)hipGraphExecDestroy(tr->kexec); tr->kexec = nullptr; }
+  if (tr->kexec_run) { (void)hipGraphExecDestroy(tr->kexec_run); tr->kexec_run = nullptr; }
+  tr->kexec_run_count = 0;
+  tr->kwarm = false;
+}
 static void drop_graph(v4l_trainer* tr) {
+  drop_kl_graph(tr);
   drop_ppo_graph(tr);
   drop_vmpo_graph(tr);
   drop_a2c_graph(tr);
@@ -3879,6 +3887,7 @@ static int check_vmpo_args(const v4l_trainer* tr, const v4l_rollout* ro, int n, 
               "loss kernel takes one log sigma per action column");
   V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_vmpo: a categorical policy (v4l_net_set_categorical) runs under the A2C and REINFORCE updates "
               "only: the V-MPO loss kernel and its KL are Gaussian");
+  V4L_REQUIRE(tr->kl_all == nullptr, "v4l_trainer_vmpo: no KL early stop (v4l_trainer_kl_stop) in a V-MPO run");
   V4L_REQUIRE(tr->vmpo != nullptr, "v4l_trainer_vmpo_actor_grads: no V-MPO state (v4l_trainer_vmpo_init)");
   V4L_REQUIRE(n <= tr->vmpo_n_max, "v4l_trainer_vmpo_actor_grads: n = %d is over the V-MPO block's n_max = %d", n, tr->vmpo_n_max);
   V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_vmpo_actor_grads: V-MPO runs in a single process");
@@ -4267,6 +4276,7 @@ static int check_a2c_args(const v4l_trainer* tr, const v4l_rollout* ro, int n, c
               "v4l_trainer_a2c: A2C runs state-MLP nets (V4L_NET_MLP) only: the reference's A2C raises on a shared encoder");
   V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_a2c: A2C runs in a single process");
   V4L_REQUIRE(tr->skip_all == nullptr, "v4l_trainer_a2c: no skipping of non-finite steps (v4l_trainer_begin_guarded) in an A2C run");
+  V4L_REQUIRE(tr->kl_all == nullptr, "v4l_trainer_a2c: no KL early stop (v4l_trainer_kl_stop) in an A2C run");
   return 0;
 }
 // a2c.py:76-77, 84-85 (values = vf(obs), vf_loss, vf_loss.backward()): v4l_trainer_critic_grads' launches for a state-MLP net with
@@ -4451,6 +4461,7 @@ static int check_reinforce_args(const v4l_trainer* tr, const v4l_rollout* ro, in
   V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_reinforce: REINFORCE runs in a single process");
   V4L_REQUIRE(tr->skip_all == nullptr,
               "v4l_trainer_reinforce: no skipping of non-finite steps (v4l_trainer_begin_guarded) in a REINFORCE run");
+  V4L_REQUIRE(tr->kl_all == nullptr, "v4l_trainer_reinforce: no KL early stop (v4l_trainer_kl_stop) in a REINFORCE run");
   return 0;
 }
 // reinforce.py:52-63 (pf.update(obs, acts), policy_loss, policy_loss.backward())
@@ -4513,6 +4524,131 @@ int v4l_trainer_reinforce_graph_counts(const v4l_trainer* tr, int64_t* captures,
   V4L_REQUIRE(tr && captures && replays, "v4l_trainer_reinforce_graph_counts: null argument");
   *captures = tr->reinforce_captures;
   *replays = tr->reinforce_replays;
+  return 0;
+}
+
+// ---- the opt-in KL early stop of a run of PPO updates (PPO(target_kl=...)). An armed update is PPO's update with
+// one more launch (kl_stop_kernel behind the policy's backward) and the clip_adam_kernel<WD, true> instantiation, which honours
+// the latch. It runs through entry points, a graph key and graph handles of its own, on the graphed driver of the learners with
+// one record array (the KL array takes the record array's place): v4l_trainer_update_next / _update_run, the stages they call
+// and their graphs are not touched.
+int v4l_trainer_kl_stop(v4l_trainer* tr, double target_kl, float* kl_all_dev, void* stream) {
+  V4L_REQUIRE(tr && tr->bound, "v4l_trainer_kl_stop: the trainer is not bound");
+  if (kl_all_dev == nullptr) {  // disarm
+    tr->kl_all = nullptr; tr->kl_thresh = 0.0;
+    return 0;
+  }
+  V4L_REQUIRE(target_kl > 0.0 && target_kl <= 3.0e38, "v4l_trainer_kl_stop: target_kl must be a positive finite number (got %g)", target_kl);
+  V4L_REQUIRE(tr->comm == nullptr, "v4l_trainer_kl_stop: the KL early stop runs in a single process (each rank would decide on its own shard)");
+  V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_kl_stop: the KL early stop belongs to the PPO update, which takes Gaussian policies");
+  if (tr->kl_thresh != 1.5 * target_kl) drop_kl_graph(tr);  // (baked into the captured kl_stop launches; the array is in the key)
+  tr->kl_all = kl_all_dev;
+  tr->kl_thresh = 1.5 * target_kl;  // the factor of Spinning Up and Stable-Baselines3
+  hipLaunchKernelGGL(kl_arm_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, tr->ctl);  // the run opens with a cleared latch
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
+static int check_kl_args(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, const float* kl_all_dev) {
+  int rc = check_update_args(tr, ro, n, hp);
+  if (rc) return rc;
+  V4L_REQUIRE(kl_all_dev != nullptr && kl_all_dev == tr->kl_all, "v4l_trainer_kl_update: arm the run first (v4l_trainer_kl_stop, after v4l_trainer_begin)");
+  V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_kl_update: the PPO loss kernels are Gaussian");
+  V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_kl_update: the KL early stop runs in a single process");
+  return 0;
+}
+// adam_step's launch for an armed run: the same arguments, the instantiation that reads the latch (the norm partials as adam_step
+// takes them from the backward's reduce launch, or summed again)
+static int adam_step_kl(v4l_trainer* tr, v4l_net* net, float* g, float* m, float* v, const v4l_ppo_hyper* hp, int which,
+                        float* norm_out, hipStream_t s, bool close_update) {
+  int gb = (int)std::min<int64_t>(GRAD_NORM_PARTS, cdiv64(net->total_params, 1024));
+  const float* part = tr->norm_part + which * GRAD_NORM_PARTS;
+  const float* extra = nullptr;
+  int nextra = 0;
+  if (int rc = check_hyper(hp)) return rc;
+  g_op = "optim";
+  if (net->red_blocks > 0 && net->red_blocks <= ADAM_MAX_PARTS && net->red_grads == g) {
+    part = net->d_sq;
+    gb = net->red_blocks;
+    net->red_blocks = 0;  // consumed
+    if (net->logstd >= 0) { extra = g + net->params[net->logstd].goff; nextra = (int)net->params[net->logstd].numel; }
+    V4L_REQUIRE(nextra <= 64, "internal: log sigma wider than a wave");
+  } else {
+    V4L_KLAUNCH("grad_sumsq", 0, s, grad_sumsq_kernel, dim3(gb), dim3(256), 0, s, g, net->total_params, tr->norm_part + which * GRAD_NORM_PARTS);
+    V4L_LAUNCH_CHECK();
+  }
+  const unsigned nf_exempt = tr->pf->cfg.out_dim == 1 ? 1u << ST_LS_STD : 0u;
+#define V4L_CLIP_ADAM_KL(WD_)                                                                                                       \
+  V4L_KLAUNCH("clip_adam", 0, s, (clip_adam_kernel<WD_, true>), dim3((unsigned)net->seg_blocks), dim3(256), 0, s, net->d_segs,      \
+              (int)net->params.size(), g, m, v, part, gb, extra, nextra, hp->max_grad_norm, hp->eps, tr->ctl, which, norm_out,      \
+              close_update ? tr->ctl : (UpdCtl*)nullptr, (const float*)tr->stats_cur, tr->stats_all, tr->skip_all, nf_exempt)
+  if (!(hp->weight_decay > 0.0)) V4L_CLIP_ADAM_KL(WD_NONE);
+  else if (hp->decoupled_weight_decay) V4L_CLIP_ADAM_KL(WD_DECOUPLED);
+  else V4L_CLIP_ADAM_KL(WD_COUPLED);
+#undef V4L_CLIP_ADAM_KL
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
+// kl_stop_kernel behind the policy's backward, on the trainer's stream: by then every loss route has completed the record (the
+// fused route's fb_loss_finish_kernel runs inside the weight-grad fork, which is joined before the backward returns), and the
+// target's head rows and the stored actions are where the loss launch read them.
+static int launch_kl_stop(v4l_trainer* tr, const v4l_rollout* ro, int n, hipStream_t s) {
+  v4l_net *pf = tr->pf, *tp = tr->tpf;
+  const bool stored = ro->logp_old_dev != nullptr, sd = pf->sd();
+  float* ws_t = tr->ws + std::max(pf->layout(n).total, tr->vf->layout(n).total);
+  KlArgs q;
+  memset(&q, 0, sizeof(q));
+  q.tmean = stored ? nullptr : ws_t + tp->layout(n).out;
+  q.tlogstd = stored || sd ? nullptr : tp->p[tp->logstd];
+  q.logp_old = ro->logp_old_dev; q.acts = ro->acts_dev; q.rowidx = tr->rowidx_cur;
+  q.n = n; q.A = pf->act_dim(); q.sd = sd ? 1 : 0;
+  q.st = tr->stats_cur; q.upd_index = &tr->ctl->upd_index; q.latch = &tr->ctl->kl_stop;
+  q.kl_all = tr->kl_all; q.thresh = tr->kl_thresh;
+  g_op = "kl_stop";
+  if (pf->cfg.tanh_action) V4L_KLAUNCH("kl_stop", 0, s, kl_stop_kernel<true>, dim3(1), loss_block(n), 0, s, q);
+  else V4L_KLAUNCH("kl_stop", 0, s, kl_stop_kernel<false>, dim3(1), loss_block(n), 0, s, q);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
+static int run_kl_update(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, void* stream) {
+  int rc;
+  hipStream_t s = (hipStream_t)stream;
+  float* st = tr->stats_cur;
+  if ((rc = v4l_trainer_critic_grads(tr, ro, n, hp, stream))) return rc;
+  if ((rc = adam_step_kl(tr, tr->vf, tr->g_vf, tr->m_vf, tr->v_vf, hp, 1, st + ST_GN_VF, s, false))) return rc;
+  if ((rc = v4l_trainer_actor_grads(tr, ro, n, hp, stream))) return rc;
+  if ((rc = launch_kl_stop(tr, ro, n, s))) return rc;
+  return adam_step_kl(tr, tr->pf, tr->g_pf, tr->m_pf, tr->v_pf, hp, 0, st + ST_GN_PF, s, true);
+}
+struct KlLearner {
+  static constexpr const char* what = "kl-stop update";
+  static constexpr const char* next_name = "v4l_trainer_kl_update_next";
+  static constexpr const char* run_name = "v4l_trainer_kl_update_run";
+  static int check(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, const float* rec) {
+    return check_kl_args(tr, ro, n, hp, rec);
+  }
+  static int run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float*, void* stream) {
+    return run_kl_update(tr, ro, n, hp, stream);
+  }
+  static RecGraphState state(v4l_trainer* tr) {
+    return {&tr->kkey, &tr->kexec, &tr->kexec_run, &tr->kexec_run_count, &tr->kwarm, &tr->kl_captures, &tr->kl_replays};
+  }
+  static void drop(v4l_trainer* tr) { drop_kl_graph(tr); }
+  // (V-MPO's, A2C's and REINFORCE's graphs bake other descriptor tables in; PPO's bake the same ones and stay)
+  static void drop_others(v4l_trainer* tr) { drop_vmpo_graph(tr); drop_a2c_graph(tr); drop_reinforce_graph(tr); }
+};
+int v4l_trainer_kl_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, int use_graph, void* stream) {
+  V4L_REQUIRE(tr != nullptr, "v4l_trainer_kl_update_next: null argument");
+  return rec_update_next<KlLearner>(tr, ro, n, hp, tr->kl_all, use_graph, stream);
+}
+int v4l_trainer_kl_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, int count, int use_graph,
+                              void* stream) {
+  V4L_REQUIRE(tr != nullptr, "v4l_trainer_kl_update_run: null argument");
+  return rec_update_run<KlLearner>(tr, ro, n, hp, tr->kl_all, count, use_graph, stream);
+}
+int v4l_trainer_kl_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays) {
+  V4L_REQUIRE(tr && captures && replays, "v4l_trainer_kl_graph_counts: null argument");
+  *captures = tr->kl_captures;
+  *replays = tr->kl_replays;
   return 0;
 }
 

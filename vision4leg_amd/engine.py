@@ -600,6 +600,27 @@ class HipTrainer:
     self.begin(rowidx, stats, lr_pf, lr_vf, skip)
     self.update_next(ro, n, graph=False)
 
+  # ---- the opt-in KL early stop (PPO(target_kl=...)): begin(), kl_arm(), then kl_update_next / kl_update_run
+  def kl_arm(self, kl_all, target_kl):
+    """Arm the run begin() just opened (v4l_trainer_kl_stop; clears the device latch). kl_all: float32 [U][2] device tensor,
+    update u writes (approx_kl, latch) there; once approx_kl > 1.5 * target_kl every later optimiser step of the run is skipped on
+    the device, starting with that update's policy step. Keep it at one address from run to run: the graph is keyed on it."""
+    self._run = self._run + (kl_all,)  # keep alive
+    check(self.L.v4l_trainer_kl_stop(self.h, float(target_kl), _ptr(kl_all), _stream()), "v4l_trainer_kl_stop")
+    self._guarded = True  # an armed run may skip steps: the device holds the counts afterwards
+
+  def kl_update_next(self, ro, n, graph=True):
+    """The next update of an armed run (v4l_trainer_kl_update_next): PPO's update plus the kl_stop launch, on graphs of its own."""
+    self._call_update("v4l_trainer_kl_update_next", ro, n, (int(graph),), 1)
+
+  def kl_update_run(self, ro, n, count, graph=True):
+    """The next `count` updates of an armed run: with graph=True ONE hipGraph replay for all of them (v4l_trainer_kl_update_run)."""
+    self._call_update("v4l_trainer_kl_update_run", ro, n, (int(count), int(graph)), int(count))
+
+  def kl_graph_counts(self):
+    """-> (armed-update graphs instantiated, their replays launched) since this trainer was created."""
+    return self._graph_counts("v4l_trainer_kl_graph_counts")
+
   # phases, for the data-parallel schedule (all-reduce between grads and step); begin() first
   def stats_cur(self):
     if getattr(self, "_stats_cur", None) is None or self._stats_cur_ctl is not self.ctl:

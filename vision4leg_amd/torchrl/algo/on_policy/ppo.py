@@ -196,7 +196,7 @@ class PPO:
                  opt_epochs=10, clipped_value_loss=False, shuffle=True, tau=None, gae=True, env=None,
                  replay_buffer=None, collector=None, logger=None, grad_clip=None, discount=0.99, num_epochs=3000,
                  batch_size=128, device="cpu", save_interval=100, eval_interval=1, save_dir=None, skip_nonfinite_steps=False,
-                 save_train_state=False, resume=None, optimizer_kwargs=None, **kwargs):
+                 save_train_state=False, resume=None, optimizer_kwargs=None, target_kl=None, **kwargs):
         # torch.optim.Adam / AdamW, a functools.partial of either, or "Adam" / "AdamW" + optimizer_kwargs (JSON configs): resolved
         # the way the reference would build it, `optimizer_class(params, lr=..., eps=1e-5)` (a2c.py:30-40); anything else raises
         opt = hip_optim.resolve(optimizer_class, optimizer_kwargs, lr=plr, eps=self._call_eps)
@@ -210,6 +210,21 @@ class PPO:
             if _dist_world() > 1 or forced:
                 raise NotImplementedError("vision4leg_amd: GaussianContPolicy (log-std from the head) runs in a single process: "
                                           "its data-parallel update (world_size > 1 / V4L_FORCE_DP_PHASES) is not verified")
+        # opt-in (config "target_kl"): the KL early stop of an epoch's optimiser steps, decided on the device.
+        # None (the reference has no such option): nothing of an update changes.
+        if target_kl is not None:  # before anything touches a device
+            ok = isinstance(target_kl, (int, float, np.integer, np.floating)) and not isinstance(target_kl, bool)
+            if not ok or not (0.0 < float(target_kl) < float("inf")):
+                raise ValueError("vision4leg_amd: target_kl must be a positive finite number or None (got %r)" % (target_kl,))
+            forced = (os.environ.get("V4L_FORCE_DP_PHASES", "0") != "0" and torch.distributed.is_available()
+                      and torch.distributed.is_initialized())
+            if _dist_world() > 1 or forced:
+                raise NotImplementedError("vision4leg_amd: target_kl runs in a single process: data parallel (world_size > 1 / "
+                                          "V4L_FORCE_DP_PHASES) each rank would decide the stop on its own shard")
+            target_kl = float(target_kl)
+        self.target_kl = target_kl
+        self.last_kl_stop = None  # (epoch, index of the update that set the latch) of the last stopped run, or None
+        self.kl_stops = 0         # runs (epochs) stopped so far; neither is part of the train state
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("vision4leg_amd: PPO needs a GPU device (got %s); there is no CPU path" % self.device)
@@ -583,10 +598,15 @@ class PPO:
             if isinstance(self.replay_buffer, rb.DeviceOnPolicyReplayBuffer):
                 self._update_epoch_resident()
                 return
+            u = 0
             for _ in range(self.opt_epochs):
                 for batch in self.replay_buffer.one_iteration(self.batch_size, self.sample_key, self.shuffle):
                     infos = self.update(batch)
                     self.logger.add_update_info(infos)
+                    if infos.get("kl_stop"):  # target_kl: the update that reported the stop is the epoch's last (both loops end)
+                        self._note_kl_stop(u)
+                        return
+                    u += 1
 
     def _epoch_rowidx(self, passes):
         """The row lists of all minibatches of an epoch, `passes` times over the samples -> int32 [U][n] device tensor."""
@@ -601,8 +621,14 @@ class PPO:
         U = len(rowidx)
         stats = torch.zeros(U, _lib.V4L_STATS, dtype=torch.float32, device=self.device)
         self.run_updates(ro, rowidx, stats)
-        flags = None
-        if self.skip_nonfinite_steps:  # records and flags share one allocation: still one device->host copy
+        flags = kl = None
+        if self.target_kl is not None:  # records, flags and KL columns share one allocation: still one device->host copy
+            rec = self._rec_buf.cpu()
+            host = rec[:U * _lib.V4L_STATS].view(U, _lib.V4L_STATS).numpy()
+            if self.skip_nonfinite_steps:
+                flags = rec[U * _lib.V4L_STATS:U * (_lib.V4L_STATS + 2)].view(torch.int32).view(U, 2).numpy()
+            kl = rec[U * (_lib.V4L_STATS + 2):].view(U, 2).numpy()
+        elif self.skip_nonfinite_steps:  # records and flags share one allocation: still one device->host copy
             rec = self._rec_buf.cpu()
             host = rec[:U * _lib.V4L_STATS].view(U, _lib.V4L_STATS).numpy()
             flags = rec[U * _lib.V4L_STATS:].view(torch.int32).view(U, 2).numpy()
@@ -613,14 +639,24 @@ class PPO:
         self._note_skipped(spf, svf)
         self._note_f16_saturation(float(host[:, _lib.ST_F16_SAT].sum()))
         for u, row in enumerate(host):
-            self.logger.add_update_info(self._info(row, None if flags is None else flags[u]))
+            self.logger.add_update_info(self._info(row, None if flags is None else flags[u], None if kl is None else kl[u]))
+            if kl is not None and kl[u][1] != 0:  # the updates after the stop changed nothing: the logger gets none of them
+                self._note_kl_stop(u)
+                break
 
-    def _info(self, row, flags):
-        """The logger's info dict of one update: the 18 reference keys, and with the guard on skipped/pf and skipped/vf (0 / 1)."""
+    def _info(self, row, flags, kl=None):
+        """The logger's info dict of one update: the 18 reference keys, with the guard on skipped/pf and skipped/vf (0 / 1), and
+        with target_kl approx_kl and kl_stop (0 / 1)."""
         info = {k: float(row[j]) for j, k in enumerate(_lib.STAT_KEYS)}
         if flags is not None:
             info["skipped/pf"], info["skipped/vf"] = int(flags[0] != 0), int(flags[1] != 0)
+        if kl is not None:
+            info["approx_kl"], info["kl_stop"] = float(kl[0]), int(kl[1] != 0)
         return info
+
+    def _note_kl_stop(self, u):
+        self.last_kl_stop = (self.current_epoch, int(u))
+        self.kl_stops += 1
 
     def _note_skipped(self, spf, svf):
         if spf or svf:
@@ -644,12 +680,48 @@ class PPO:
                               "want V4L_COMPUTE=bf16." % (int(count), 32768.0, _lib.ST_F16_SAT), RuntimeWarning)
             self.f16_saturated += count
 
-    def run_updates(self, ro, rowidx, stats, skip=None):
+    def _run_updates_kl(self, ro, rowidx, stats, skip, kl):
+        """run_updates with target_kl: the armed run (HipTrainer.kl_arm / kl_update_run, graphs of their own), by run_updates'
+        switches. Records, guard flags and the KL columns [U][2] (approx_kl, latch) share one allocation."""
+        tr = self.trainer
+        U, n = rowidx.shape
+        if getattr(self, "_rowidx_buf", None) is None or self._rowidx_buf.shape != rowidx.shape:
+            self._rowidx_buf = torch.empty_like(rowidx)
+            self._rec_buf = torch.zeros(U * (_lib.V4L_STATS + 4), dtype=torch.float32, device=self.device)
+            self._stats_buf = self._rec_buf[:U * _lib.V4L_STATS].view(U, _lib.V4L_STATS)
+            self._skip_buf = self._rec_buf[U * _lib.V4L_STATS:U * (_lib.V4L_STATS + 2)].view(torch.int32).view(U, 2)
+            self._kl_buf = self._rec_buf[U * (_lib.V4L_STATS + 2):].view(U, 2)
+        self._rowidx_buf.copy_(rowidx)
+        cur = torch.cuda.current_stream(self.device)
+        tr.stream.wait_stream(cur)
+        with torch.cuda.stream(tr.stream):
+            tr._pre(n)
+            tr.begin(self._rowidx_buf, self._stats_buf, self.pf_optimizer.lr, self.vf_optimizer.lr,
+                     self._skip_buf if self.skip_nonfinite_steps else None)
+            tr.kl_arm(self._kl_buf, self.target_kl)
+            self.training_update_num += U
+            if self.use_graph and os.environ.get("V4L_EPOCH_GRAPH", "1") != "0":
+                tr.kl_update_run(ro, n, U, graph=True)
+            else:
+                for _ in range(U):
+                    tr.kl_update_next(ro, n, graph=self.use_graph)
+            stats.copy_(self._stats_buf)
+            if skip is not None:
+                skip.copy_(self._skip_buf)
+            if kl is not None:
+                kl.copy_(self._kl_buf)
+        cur.wait_stream(tr.stream)
+
+    def run_updates(self, ro, rowidx, stats, skip=None, kl=None):
         """All minibatch updates of an epoch: rowidx [U][n] int32 (device), stats [U][V4L_STATS] (device); skip: None or an
-        int32 [U][2] device tensor that receives the guard's skipped-step flags (skip_nonfinite_steps).
+        int32 [U][2] device tensor that receives the guard's skipped-step flags (skip_nonfinite_steps); kl (target_kl only): None
+        or a float32 [U][2] device tensor that receives (approx_kl, latch) per update — every optimiser step after the update that
+        set the latch is skipped on the device; the launches still run (a stop saves no GPU time here).
         The whole run is ONE hipGraph replay on the trainer's stream (round 6; one replay per update with V4L_EPOCH_GRAPH=0) — on one
         GPU, and data-parallel with the library's own communicator (V4L_DP_COMM=rccl: both all-reduces are nodes of that graph). With torch.distributed doing the exchange
         (the data-parallel default) an update is four eager phases with one all-reduce per optimiser step between them."""
+        if self.target_kl is not None:
+            return self._run_updates_kl(ro, rowidx, stats, skip, kl)
         tr = self.trainer
         U, n = rowidx.shape
         # the captured graph is keyed on these addresses: keep them stable from epoch to epoch
@@ -718,7 +790,9 @@ class PPO:
         return n, [up(batch[k]).reshape((n, -1) if k == "acts" else n) for k in keys]
 
     def update(self, batch):
-        """One minibatch update from a reference-style host batch (ppo.py:125-153). Returns the 18-key info."""
+        """One minibatch update from a reference-style host batch (ppo.py:125-153). Returns the 18-key info (plus skipped/* with
+        the guard, approx_kl and kl_stop with target_kl: here a run is this one update, so kl_stop = 1 says that its policy step
+        was skipped and that the caller's loops over the epoch's minibatches should end, as update_per_epoch's do)."""
         dev = self.device
         with torch.cuda.device(dev):
             n, arrays = self._upload_batch(batch, ("acts", "advs", "estimate_returns", "values"))
@@ -726,8 +800,15 @@ class PPO:
             ro = HipTrainer.rollout(self._stage[0], self._stage[1], *arrays)
             stats = torch.zeros(1, _lib.V4L_STATS, dtype=torch.float32, device=dev)
             skip = torch.zeros(1, 2, dtype=torch.int32, device=dev) if self.skip_nonfinite_steps else None
+            kl = None
             tr = self.trainer
-            if not self.dp_phases:
+            if self.target_kl is not None:  # a run of one armed update, eager like the one below
+                kl = torch.zeros(1, 2, dtype=torch.float32, device=dev)
+                tr._pre(n)
+                tr.begin(None, stats, self.pf_optimizer.lr, self.vf_optimizer.lr, skip)
+                tr.kl_arm(kl, self.target_kl)
+                tr.kl_update_next(ro, n, graph=False)
+            elif not self.dp_phases:
                 tr.update(ro, None, n, self.pf_optimizer.lr, self.vf_optimizer.lr, stats, skip)
             else:
                 tr._pre(n)
@@ -735,12 +816,13 @@ class PPO:
                 self._update_phases(ro, n)
             host = stats[0].cpu().numpy()
             flags = skip.cpu().numpy() if skip is not None else None
+            klh = kl.cpu().numpy() if kl is not None else None
         # the device-side tripwire, as in _update_epoch_resident
         spf, svf = _check_update_records(host[None], flags, self.skip_nonfinite_steps,
                                          lambda u: "minibatch update %d" % self.training_update_num)
         self._note_skipped(spf, svf)
         self._note_f16_saturation(float(host[_lib.ST_F16_SAT]))
-        return self._info(host, None if flags is None else flags[0])
+        return self._info(host, None if flags is None else flags[0], None if klh is None else klh[0])
 
     # ---- outer loop (rl_algo.py:97-168) ----------------------------------------------------------------
     def train(self):
