@@ -19,7 +19,7 @@
  *     fp32 accumulate (round 6: bf16's MFMA rate and bytes, three more significand bits — 8 x closer to the fp32 reference;
  *     half's 5 exponent bits are why its backward runs on scaled loss-gradient rows: v4l_net_grad_scale).
  *
- * Environment switches read by the library: 21 (round 4: 37 — the ones no test referenced went in round 5, their fast-path value
+ * Environment switches read by the library: 22 (round 4: 37 — the ones no test referenced went in round 5, their fast-path value
  * is now compiled in; V4L_VIS17 came with the native 16-token kernels). tests/test_cpu.py keeps this list and the source in step. Three configure a run, the others are DIAGNOSTIC: every one of them backs a bit-equality / cross-check test
  * under tests/ that compares a fused kernel or a launch schedule against the general one. Read when first needed unless (per call).
  *   run:   V4L_TRACE (launch / graph log on stderr), V4L_RCCL_LIB (RCCL library to dlopen; default librccl.so.1), V4L_ROCTX=1 (roctx
@@ -42,6 +42,8 @@
  *   V4L_LAYER_TAPS            the wave-per-sample layer kernels and the fused conv backward also write every intermediate into
  *                             its v4l_net_ws_offset slot (production keeps them on chip) (per call)
  *   V4L_CONV_BWD_BLOCKS, V4L_CONV3_WGRAD_BLOCKS   persistent-block counts (tests force ragged and many-samples-per-block shapes)
+ *   V4L_WGRAD_TR=0|1|2|3   16-bit modes: the fused conv backward's weight-grad operands by transposed LDS reads: 0 the element
+ *                          gathers, 1 (default) everywhere, 2 dW2 / dW1 only, 3 dW3 only (bit-identical results)
  *   V4L_GEMM_DEEP_MIN_M       smallest row count the general path's dense layers send to gemm_nt_deep_kernel (default 256) (per call)
  *   V4L_ROLLOUT_DENSE_SPLIT   NatureCNN nets' rollout step: the dense layers as three launches instead of one launch with
  *                             device-side hand-overs (per call)

@@ -12,7 +12,7 @@ actor=policies.RolloutActor(pf,vf,E)
 obs=torch.randn(E, 93+16384, device=dev)
 for i in range(20): actor.step(obs)
 L=_lib.lib(); L.v4l_debug_stamps.argtypes=[C.c_void_p]; L.v4l_debug_stamps.restype=C.c_int
-buf=(C.c_longlong*32)(); L.v4l_debug_stamps(buf)
+buf=(C.c_longlong*128)(); L.v4l_debug_stamps(buf)
 st=np.array(buf[:9],dtype=np.int64)
 names=["load x","in_proj","attention","out_proj+res","LN1","FF1","FF2+res","LN2 out"]
 d=np.diff(st)

@@ -17,7 +17,7 @@ for it in range(3):
     hip.backward(st_, im, n, dout, grads)
 torch.cuda.synchronize()
 L=_lib.lib(); L.v4l_debug_stamps.argtypes=[C.c_void_p]; L.v4l_debug_stamps.restype=C.c_int
-buf=(C.c_longlong*48)(); L.v4l_debug_stamps(buf)
+buf=(C.c_longlong*128)(); L.v4l_debug_stamps(buf)  # the library copies all 128 stamps of g_inf_stamps (csrc/infer.h)
 st=np.array(buf[16:23],dtype=np.int64)
 names=["loads->LDS","dgrad3 (gather GEMM)","bias2+wgrad2","dgrad2 (gather GEMM)","bias1","wgrad1"]
 print("bwd_conv_kernel block 0, 4th sample, phase cycles (clock64, 100 MHz s_memtime or shader clock):")

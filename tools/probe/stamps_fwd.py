@@ -16,6 +16,6 @@ L=_lib.lib(); L.v4l_debug_stamps.argtypes=[C.c_void_p]; L.v4l_debug_stamps.resty
 for train in (True, False):
     for it in range(3): hip.forward(st_, im, n, train=train)
     torch.cuda.synchronize()
-    buf=(C.c_longlong*48)(); L.v4l_debug_stamps(buf)
+    buf=(C.c_longlong*128)(); L.v4l_debug_stamps(buf)
     st=np.array(buf[:9],dtype=np.int64)
     print("train" if train else "infer", np.diff(st), "in_proj: gemm +%d epi +%d | linear1: gemm +%d epi +%d" % (buf[9]-buf[1], buf[10]-buf[9], buf[11]-buf[5], buf[12]-buf[11]))

@@ -8,6 +8,7 @@
 //      -> softmax-attention' -> dqkv -> (Win^T) + dz1 -> dx_in
 #pragma once
 #include "infer.h"
+#include "tr_maps.h"
 
 namespace v4l {
 
@@ -779,7 +780,8 @@ __global__ __launch_bounds__(256) void bwd_layer_kernel(BwdLayerStack stk, BwdHe
 //     64 KB of weights live in LDS in fragment order for the block's whole life (bf16);
 //   * dc2 and dc1 exist only as MFMA operands: the data-grad epilogues store them in T, both as [pixel][co] (next data-grad)
 //     and transposed [co][pixel] (weight-grad fragments = single 16-byte LDS reads), and add the bias gradients from the same
-//     registers;
+//     registers; in the 16-bit modes (TR) there is no transposed copy: the weight-grads take BOTH operands out of the
+//     [pixel][channel] images (and the natural image) by transposed LDS reads, two per fragment;
 //   * nothing is waited for where it is requested: the image goes global -> LDS by DMA under dW2 / conv2' (LDS-only phases),
 //     the NEXT sample's dc3 / c2 / c1 are requested under dW1 and filed after it.
 struct BwdConv {
@@ -795,8 +797,11 @@ struct BwdConv {
   int n;
   void *t_dc2, *t_dc1;              // test taps (null in production): dc2 [n*36][64], dc1 [n*225][32] as the kernel holds them (T)
 };
-template <typename T> struct BwdConvLds {
+// TR (16-bit T only): the weight-grad operands come out of the pixel-major images by transposed reads (frag_tr, common.h; the address
+// maps: tr_maps.h) — dc2^T is gone, dc1 is kept as [256 pixels][32 co + 8], and a 2 KB table holds dW1's per-lane image offsets
+template <typename T, bool TR = false> struct BwdConvLds {
   static constexpr bool B16 = sizeof(T) == 2;
+  static_assert(!TR || B16, "transposed LDS reads are 16-bit only");
   static constexpr int LF = 64 + 4;                 // c2 rows (fp32, the ReLU mask of conv3')
   static constexpr int LC1 = 32 + (B16 ? 8 : 0);    // c1 rows (T)
   static constexpr int IMGP = B16 ? 1 : 2;          // image passes (fp32: two channels at a time)
@@ -806,13 +811,18 @@ template <typename T> struct BwdConvLds {
   static constexpr size_t dc3_b = (size_t)17 * LT * sizeof(T);   // + one zero row (taps that fall outside the 4x4 plane)
   static constexpr size_t c2_b = (size_t)36 * LF * 4;
   static constexpr size_t dc2_b = (size_t)48 * LT * sizeof(T);   // conv2' operand; rows 36..47: zeros (MFMA padding / out-of-plane taps)
-  static constexpr size_t dc2T_b = (size_t)64 * LP2 * sizeof(T); // dW2 operand; pixels 36..63: zeros
+  static constexpr size_t dc2T_b = TR ? 0 : (size_t)64 * LP2 * sizeof(T); // dW2 operand; pixels 36..63: zeros
   static constexpr size_t c1_b = ((size_t)225 * LC1 * sizeof(T) + 15) / 16 * 16;
-  static constexpr size_t dc1_b = (size_t)32 * LP1 * sizeof(T);  // dW1 operand (dc1^T); pixels 225..255: zeros
+  static constexpr int LD1 = 32 + 8;                // TR: dc1 rows [pixel 0..255][co]
+  static constexpr size_t dc1_b = (size_t)(TR ? 256 * LD1 : 32 * LP1) * sizeof(T);  // dW1 operand (dc1^T; TR: dc1); pixels 225..255: zeros
   static constexpr size_t img_b = (size_t)(4 / IMGP) * 4096 * sizeof(T);
   static constexpr size_t w2_b = B16 ? (size_t)4 * 32 * 256 * sizeof(T) : 0;  // conv2' weights, resident in fragment order (bf16 only)
-  static constexpr size_t bytes = dc3_b + c2_b + dc2_b + dc2T_b + c1_b + dc1_b + img_b + w2_b;
+  static constexpr size_t tab_b = TR ? (size_t)8 * 64 * 4 : 0;   // TR: dW1's image offsets [K step][lane], h = 0 | h = 1 << 16
+  static constexpr size_t bytes = dc3_b + c2_b + dc2_b + dc2T_b + c1_b + dc1_b + img_b + w2_b + tab_b;
   static_assert(bytes <= 160 * 1024, "one block per CU");
+  static_assert(!TR || (LC1 == trmap::LC1 && LT == trmap::LT && LD1 == trmap::LD1), "tr_maps.h describes these rows");
+  static_assert((dc3_b + c2_b) % 16 == 0 && (dc3_b + c2_b + dc2_b + dc2T_b) % 16 == 0 && c1_b % 16 == 0 && dc1_b % 16 == 0,
+                "every image starts on a 16-byte boundary (transposed reads: 8)");
 };
 
 // MFMA operand (row = lane&15, 8 consecutive contraction indices 8*(lane>>4)+j) from 8 scalar values
@@ -878,10 +888,12 @@ __device__ __forceinline__ void gather_gemm(f32x4 (&acc)[MT][NT], const T* __res
 // A16 (bf16 only): a.c1 / a.c2 hold the activations in T — the type this kernel rounds them to when it files them into LDS
 // anyway (c1: MFMA operand; c2: only its sign is used, as the ReLU mask of conv3'), so the results are bit-identical and the
 // launch reads 19 KB less per sample (the training encoder writes 19 KB less).
-template <typename T, bool A16 = false>
+// TR (16-bit T): dW2's and dW1's operands by transposed LDS reads; every pixel keeps its K slot, so every MFMA sees the operand
+// bits of the gathers below in the same order (tools/host/tr_maps_check.cpp checks the maps, V4L_WGRAD_TR=0 selects TR = false)
+template <typename T, bool A16 = false, bool TR = false>
 __global__ __launch_bounds__(512) void bwd_conv_kernel(BwdConv a) {
   static_assert(!A16 || sizeof(T) == 2, "A16: activations saved in the bf16 operand type");
-  typedef BwdConvLds<T> LY;
+  typedef BwdConvLds<T, TR> LY;
   typedef typename Frag<T>::type frag_t;
   constexpr int NTH = 512;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -894,6 +906,7 @@ __global__ __launch_bounds__(512) void bwd_conv_kernel(BwdConv a) {
   T* sdc1T = reinterpret_cast<T*>(smem + o_c1 + LY::c1_b);
   T* simg = reinterpret_cast<T*>(smem + o_c1 + LY::c1_b + LY::dc1_b);
   T* sw2 = reinterpret_cast<T*>(smem + o_c1 + LY::c1_b + LY::dc1_b + LY::img_b);
+  uint32_t* stab = reinterpret_cast<uint32_t*>(smem + o_c1 + LY::c1_b + LY::dc1_b + LY::img_b + LY::w2_b);  // (TR)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, g = lane >> 4, qr = g * 4;
   // weight-grad tiles of this wave
@@ -910,8 +923,21 @@ __global__ __launch_bounds__(512) void bwd_conv_kernel(BwdConv a) {
   float b2r[4] = {0.f, 0.f, 0.f, 0.f};  // waves 0..3: co = 16*(wave&3) + 4*(lane>>4) + i, partial over the lane's pixels
   float b1r[4] = {0.f, 0.f, 0.f, 0.f};  // co = 16*(wave&1) + 4*(lane>>4) + i
   for (int i = tid; i < 12 * LY::LT; i += NTH) sdc2t[36 * LY::LT + i] = (T)0.f;
-  for (int i = tid; i < 64 * LY::LP2; i += NTH) sdc2T[i] = (T)0.f;
-  for (int i = tid; i < 32 * LY::LP1; i += NTH) sdc1T[i] = (T)0.f;
+  if constexpr (!TR) {
+    for (int i = tid; i < 64 * LY::LP2; i += NTH) sdc2T[i] = (T)0.f;
+  }
+  for (int i = tid; i < (int)(LY::dc1_b / sizeof(T)); i += NTH) sdc1T[i] = (T)0.f;
+  // TR: the per-lane offsets of the gathered operands do not change from sample to sample. dW2's c1 pixels: 4 registers; dW1's
+  // image pixels (a division by 15 each): a table [K step][lane] in LDS, one 4-byte read per step
+  int a2o[2][2] = {{0, 0}, {0, 0}};
+  if constexpr (TR) {
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) a2o[st][h] = trmap::dw2_a_lane(st, lane, h);
+    for (int i = tid; i < 8 * 64; i += NTH)
+      stab[i] = (uint32_t)trmap::dw1_a_lane(i >> 6, i & 63, 0) | (uint32_t)trmap::dw1_a_lane(i >> 6, i & 63, 1) << 16;
+  }
   for (int i = tid; i < LY::LT; i += NTH) sdc3[16 * LY::LT + i] = (T)0.f;
   constexpr int CH = 4 / LY::IMGP;  // image channels resident at a time
 
@@ -1046,8 +1072,10 @@ __global__ __launch_bounds__(512) void bwd_conv_kernel(BwdConv a) {
             const float d2 = mk.z > 0.f ? acc[m][0][2] + hi.z : 0.f, d3 = mk.w > 0.f ? acc[m][0][3] + hi.w : 0.f;
             st4(sdc2t + px * LY::LT + c4, d0, d1, d2, d3);  // [pixel][co]: the A operand of conv2' below
             if (a.t_dc2 != nullptr) st4(reinterpret_cast<T*>(a.t_dc2) + ((int64_t)smp * 36 + px) * 64 + c4, d0, d1, d2, d3);
-            T* tp = sdc2T + c4 * LY::LP2 + px;              // [co][pixel]: dW2's column fragments
-            tp[0] = (T)d0; tp[LY::LP2] = (T)d1; tp[2 * LY::LP2] = (T)d2; tp[3 * LY::LP2] = (T)d3;
+            if constexpr (!TR) {
+              T* tp = sdc2T + c4 * LY::LP2 + px;            // [co][pixel]: dW2's column fragments
+              tp[0] = (T)d0; tp[LY::LP2] = (T)d1; tp[2 * LY::LP2] = (T)d2; tp[3 * LY::LP2] = (T)d3;
+            }
             b2r[0] += d0; b2r[1] += d1; b2r[2] += d2; b2r[3] += d3;
           }
         }
@@ -1057,15 +1085,36 @@ __global__ __launch_bounds__(512) void bwd_conv_kernel(BwdConv a) {
     CONV_STAMP(2);
     // the image (contiguous, unpadded in LDS) goes global -> LDS directly: four 16-byte DMA transfers per lane, no staging
     // registers (LDS destination = wave-uniform base + lane * 16). Issued here, it lands while dW2 and conv2' run out of LDS.
+    // TR: issued behind dW2 — the compiler cannot tell that a transposed read (an intrinsic: no alias information) stays clear of
+    // the DMA's destination and waits for vmcnt(0) in front of the first one, which would put the whole transfer in front of dW2
+    auto image_dma = [&]() {
 #pragma unroll
-    for (int k = 0; k < CH * 4096 / V / NTH; ++k)
-      __builtin_amdgcn_global_load_lds((const V4L_GLOBAL void*)(gimg + (int64_t)(tid + k * NTH) * V),
-                                       (__attribute__((address_space(3))) void*)(simg + ((tid & ~63) + k * NTH) * V), 16, 0, 0);
+      for (int k = 0; k < CH * 4096 / V / NTH; ++k)
+        __builtin_amdgcn_global_load_lds((const V4L_GLOBAL void*)(gimg + (int64_t)(tid + k * NTH) * V),
+                                         (__attribute__((address_space(3))) void*)(simg + ((tid & ~63) + k * NTH) * V), 16, 0, 0);
+    };
+    if constexpr (!TR) image_dma();
     // ---- dW2 += dc2^T col(c1): contraction over the 36 output pixels (two K=32 steps; pixels 36..63 of dc2^T are zeros, so
     //      the c1 side only has to stay in bounds there)
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
       frag_t fy[4];
+      if constexpr (TR) {
+        // both operands straight out of the [pixel][channel] images: dc2 as conv2' reads it (zero row 36 for pixels 36..63), c1 rows
+        // at the 8 gathered pixels of the lane group
+        const T* pb0 = sdc2t + trmap::dw2_b_lane(st, lane, 0);
+        const T* pb1 = sdc2t + trmap::dw2_b_lane(st, lane, 1);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) fy[c] = frag_tr(pb0 + c * 16, pb1 + c * 16);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const T* pa = sc1 + trmap::dw2_a_tile(kt2 + t);
+          const frag_t fx = frag_tr(pa + a2o[st][0], pa + a2o[st][1]);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) mma_k32(acc2[t][c], fx, fy[c]);
+        }
+        continue;
+      }
 #pragma unroll
       for (int c = 0; c < 4; ++c) fy[c] = *reinterpret_cast<const frag_t*>(sdc2T + (c * 16 + fr) * LY::LP2 + st * 32 + g * 8);
 #pragma unroll
@@ -1084,6 +1133,7 @@ __global__ __launch_bounds__(512) void bwd_conv_kernel(BwdConv a) {
         for (int c = 0; c < 4; ++c) mma_k32(acc2[t][c], fx, fy[c]);
       }
     }
+    if constexpr (TR) image_dma();
     CONV_STAMP(3);
     {  // ---- dc1 = conv2' (gather form): wave pair = stride-parity class (py,px) with <= 8x8 input pixels (4 row tiles); the
        //      pair splits the two 16-wide ci tiles (N = 32), so a class's 16 KB of weights are streamed once; K = 2x2 taps x 64 co
@@ -1120,8 +1170,12 @@ __global__ __launch_bounds__(512) void bwd_conv_kernel(BwdConv a) {
           const float4 mk = ld4(sc1 + p * LY::LC1 + c4);
           const float d0 = mk.x > 0.f ? acc[m][0][0] : 0.f, d1 = mk.y > 0.f ? acc[m][0][1] : 0.f;
           const float d2 = mk.z > 0.f ? acc[m][0][2] : 0.f, d3 = mk.w > 0.f ? acc[m][0][3] : 0.f;
-          T* tp = sdc1T + c4 * LY::LP1 + p;  // dc1 exists only as dW1's operand: [co][pixel]
-          tp[0] = (T)d0; tp[LY::LP1] = (T)d1; tp[2 * LY::LP1] = (T)d2; tp[3 * LY::LP1] = (T)d3;
+          if constexpr (TR) {
+            st4(sdc1T + p * LY::LD1 + c4, d0, d1, d2, d3);  // dc1 exists only as dW1's operand: [pixel][co], read transposed
+          } else {
+            T* tp = sdc1T + c4 * LY::LP1 + p;  // dc1 exists only as dW1's operand: [co][pixel]
+            tp[0] = (T)d0; tp[LY::LP1] = (T)d1; tp[2 * LY::LP1] = (T)d2; tp[3 * LY::LP1] = (T)d3;
+          }
           if (a.t_dc1 != nullptr) st4(reinterpret_cast<T*>(a.t_dc1) + ((int64_t)smp * 225 + p) * 32 + c4, d0, d1, d2, d3);
           b1r[0] += d0; b1r[1] += d1; b1r[2] += d2; b1r[3] += d3;
         }
@@ -1143,6 +1197,28 @@ __global__ __launch_bounds__(512) void bwd_conv_kernel(BwdConv a) {
       }
       if (ch1 >= h * CH && ch1 < (h + 1) * CH) {  // this wave's input channel is resident
         const T* ich = simg + (ch1 - h * CH) * 4096;
+        if constexpr (TR) {
+          // the A block's 16 columns = the k-tile's two kernel rows x 8 kx of the natural image, its rows = the lane group's 8 pixels
+          const T* pb0 = sdc1T + trmap::dw1_b_lane(0, lane, 0);
+          const T* pb1 = sdc1T + trmap::dw1_b_lane(0, lane, 1);
+#pragma unroll 4
+          for (int st = 0; st < 8; ++st) {
+            const uint32_t po = stab[st * 64 + lane];
+            const T* pa0 = ich + (po & 0xffffu);
+            const T* pa1 = ich + (po >> 16);
+            frag_t fy[2];
+#pragma unroll
+            for (int c = 0; c < 2; ++c) fy[c] = frag_tr(pb0 + st * 32 * LY::LD1 + c * 16, pb1 + st * 32 * LY::LD1 + c * 16);
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+              const int ot = trmap::dw1_a_tile(th1 * 2 + tt);
+              const frag_t fx = frag_tr(pa0 + ot, pa1 + ot);
+#pragma unroll
+              for (int c = 0; c < 2; ++c) mma_k32(acc1[c][tt], fx, fy[c]);
+            }
+          }
+          continue;
+        }
 #pragma unroll 1
         for (int st = 0; st < 8; ++st) {
           frag_t fy[2];
@@ -1215,12 +1291,18 @@ __global__ __launch_bounds__(512) void bwd_conv_kernel(BwdConv a) {
 
 // dW3 += dc3^T col(c2) (see above): persistent blocks, sample = blockIdx.x, += gridDim.x; wave w owns k-tiles 9w..9w+8 x all
 // four co-tiles, the contraction runs over the 16 output pixels (one zero-padded K=32 MFMA step per sample)
-template <typename T, bool A16 = false>
+// TR (16-bit T): dc3 and c2 are filed in T — the rounding frag_of<T> applies below — as [pixel][channel] rows and every operand is
+// two transposed reads (frag_tr, common.h; maps: tr_maps.h); lane groups 2 and 3, the zero K half, read zeroed pad rows. The fp32
+// dc3 rows stay for the bias gradient, which is summed before any rounding.
+template <typename T, bool A16 = false, bool TR = false>
 __global__ __launch_bounds__(256) void bwd_conv3_wgrad_kernel(BwdConv a) {
+  static_assert(!TR || sizeof(T) == 2, "transposed LDS reads are 16-bit only");
   typedef typename Frag<T>::type frag_t;
-  constexpr int LF = 64 + 4;
+  constexpr int LF = 64 + 4, L3 = trmap::L3;
   __shared__ __attribute__((aligned(16))) float sdc3[16 * LF];
-  __shared__ __attribute__((aligned(16))) float sc2[36 * LF];
+  __shared__ __attribute__((aligned(16))) float sc2[TR ? 4 : 36 * LF];
+  __shared__ __attribute__((aligned(16))) T sdc3t[TR ? 17 * L3 : 8];         // row 16: zeros
+  __shared__ __attribute__((aligned(16))) T sc2t[TR ? trmap::C2R * L3 : 8];  // rows 36 .. C2R - 1: zeros
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, g = lane >> 4, qr = g * 4;
   const int kt3 = wave * 9;
@@ -1268,7 +1350,17 @@ __global__ __launch_bounds__(256) void bwd_conv3_wgrad_kernel(BwdConv a) {
   };
   auto file = [&]() {
     *reinterpret_cast<float4*>(sdc3 + (tid >> 4) * LF + (tid & 15) * 4) = r3;
-    if constexpr (A16) {
+    if constexpr (TR) {
+      st4(sdc3t + (tid >> 4) * L3 + (tid & 15) * 4, r3.x, r3.y, r3.z, r3.w);
+      if constexpr (A16) {  // already T: one 16-byte store per chunk
+        *reinterpret_cast<chunk_t*>(sc2t + (tid >> 3) * L3 + (tid & 7) * 8) = q2a;
+        if (tid < 32) *reinterpret_cast<chunk_t*>(sc2t + ((256 + tid) >> 3) * L3 + (tid & 7) * 8) = q2b;
+      } else {
+        st4(sc2t + (tid >> 4) * L3 + (tid & 15) * 4, r2a.x, r2a.y, r2a.z, r2a.w);
+        st4(sc2t + ((tid + 256) >> 4) * L3 + (tid & 15) * 4, r2b.x, r2b.y, r2b.z, r2b.w);
+        if (tid + 512 < 36 * 16) st4(sc2t + ((tid + 512) >> 4) * L3 + (tid & 15) * 4, r2c.x, r2c.y, r2c.z, r2c.w);
+      }
+    } else if constexpr (A16) {
       auto put = [&](int j, const chunk_t& q) {
         float* d = sc2 + (j >> 3) * LF + (j & 7) * 8;
         *reinterpret_cast<float4*>(d) = float4{(float)q[0], (float)q[1], (float)q[2], (float)q[3]};
@@ -1282,6 +1374,13 @@ __global__ __launch_bounds__(256) void bwd_conv3_wgrad_kernel(BwdConv a) {
       if (tid + 512 < 36 * 16) *reinterpret_cast<float4*>(sc2 + ((tid + 512) >> 4) * LF + (tid & 15) * 4) = r2c;
     }
   };
+  // TR: the lane's operand rows (sample-independent) and the zero rows the k >= 16 lane groups read
+  const int b3o[2] = {trmap::dw3_b_lane(lane, 0), trmap::dw3_b_lane(lane, 1)};
+  const int a3o[2] = {trmap::dw3_a_lane(lane, 0), trmap::dw3_a_lane(lane, 1)};
+  if constexpr (TR) {
+    for (int i = tid; i < L3; i += 256) sdc3t[16 * L3 + i] = (T)0.f;
+    for (int i = tid; i < (trmap::C2R - 36) * L3; i += 256) sc2t[36 * L3 + i] = (T)0.f;
+  }
   if ((int)blockIdx.x < a.n) fetch(blockIdx.x);
   for (int smp = blockIdx.x; smp < a.n; smp += gridDim.x) {
     __syncthreads();  // the previous sample's readers are done
@@ -1297,6 +1396,18 @@ __global__ __launch_bounds__(256) void bwd_conv3_wgrad_kernel(BwdConv a) {
     }
     float v[8];
     frag_t fy[4];
+    if constexpr (TR) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) fy[c] = frag_tr(sdc3t + b3o[0] + c * 16, sdc3t + b3o[1] + c * 16);
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        const T* pa = sc2t + trmap::dw3_a_tile(kt3 + t);
+        const frag_t fx = frag_tr(pa + a3o[0], pa + a3o[1]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) mma_k32(acc3[t][c], fx, fy[c]);
+      }
+      continue;
+    }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
 #pragma unroll

@@ -114,6 +114,21 @@ template <> struct Frag<__bf16> { typedef bf16x8 type; };
 template <> struct Frag<_Float16> { typedef f16x8 type; };
 template <> struct Frag<float> { typedef f32x8 type; };
 
+// An MFMA operand out of a K-MAJOR LDS image ([k][row], 16-bit elements) by two transposed reads (ds_read_b64_tr_b16, gfx950
+// only): within each group of 16 lanes, lane 4q + p points at the 4 contiguous elements [k = 8g + q (p0) | 8g + 4 + q (p1)]
+// [rows 4p .. 4p+3] and lane (fr, g) receives row fr's k = 8g .. 8g+7, the layout mma_k32 takes. The k rows may sit at arbitrary
+// addresses (csrc/tr_maps.h holds the maps in use). Every lane's address must be 8-byte aligned, and EXEC must be all ones: the
+// gather crosses lanes, so call it under wave-uniform control flow only and pad (never mask) what is out of range.
+typedef short s16x4_t __attribute__((vector_size(8)));
+template <typename H>
+__device__ __forceinline__ typename Frag<H>::type frag_tr(const H* p0, const H* p1) {
+  static_assert(sizeof(H) == 2, "16-bit operand type");
+  typedef __attribute__((address_space(3))) s16x4_t* lds_p;
+  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)p0);
+  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)p1);
+  return __builtin_bit_cast(typename Frag<H>::type, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
 // 4 consecutive elements of one row -> one 8/16-byte store (LDS or global), T = __bf16 | _Float16 | float
 template <typename H>
 __device__ __forceinline__ void st4(H* p, float a, float b, float c, float d) {

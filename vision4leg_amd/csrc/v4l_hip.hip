@@ -221,7 +221,7 @@ struct Ctx {  // per-call view of a bound net
   int64_t slab_used;
   hipStream_t tn;      // stream weight-grad kernels go to: s, or the net's aux stream inside par_begin/par_end
   // dW3's launch can be held back by conv_stack_bwd_fused and issued by the caller (next to the dense weight-grads)
-  bool defer_conv3 = false, conv3_pending = false, conv3_a16 = false;
+  bool defer_conv3 = false, conv3_pending = false, conv3_a16 = false, conv3_tr = false;
   v4l::BwdConv conv3_args = {};
   int conv3_blocks = 0, conv3_n = 0;
   // the wave-per-sample layers' weight-grad launch (csrc/wps.h), issued with the other dense weight-grads
@@ -638,17 +638,41 @@ static bool conv_bwd_fusable(const v4l_net* N) {
          v[2].Cin == 64 && v[2].KH == 3 && v[2].stride == 1 && v[2].Cout == 64 && v[2].OH == 4 &&
          !sw_on("V4L_NO_FUSED_CONV_BWD");
 }
+// dW3's launch (bwd_conv3_wgrad_kernel) of the conv-stack backward last set up in c.conv3_*, on stream s
+template <typename T>
+static int conv3_wgrad_launch(Ctx& c, hipStream_t s) {
+  g_op = "conv3.wgrad";
+  const double fl = 2.0 * c.conv3_n * 16 * 64 * 576;
+  const dim3 grid(c.conv3_blocks), blk(256);
+  const bool a16 = c.conv3_a16, tr = c.conv3_tr;
+  if constexpr (sizeof(T) == 2) {
+    if (a16 && tr) V4L_KLAUNCH("fused_conv3_wgrad", fl, s, (bwd_conv3_wgrad_kernel<T, true, true>), grid, blk, 0, s, c.conv3_args);
+    else if (a16) V4L_KLAUNCH("fused_conv3_wgrad", fl, s, (bwd_conv3_wgrad_kernel<T, true>), grid, blk, 0, s, c.conv3_args);
+    else if (tr) V4L_KLAUNCH("fused_conv3_wgrad", fl, s, (bwd_conv3_wgrad_kernel<T, false, true>), grid, blk, 0, s, c.conv3_args);
+  }
+  if (!a16 && !tr) V4L_KLAUNCH("fused_conv3_wgrad", fl, s, bwd_conv3_wgrad_kernel<T>, grid, blk, 0, s, c.conv3_args);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
 template <typename T>
 static int conv_stack_bwd_fused(Ctx& c, const T* image, const int* rowidx, int n, const float* c1, const float* c2,
                                 const float* dc3, float* dc2_tap, float* dc1_tap) {
   v4l_net* N = c.net;
   V4L_HIP_CHECK(lds_limit<&bwd_conv_kernel<T>>(BwdConvLds<T>::bytes));
-  if constexpr (sizeof(T) == 2) V4L_HIP_CHECK(lds_limit<&bwd_conv_kernel<T, true>>(BwdConvLds<T>::bytes));
+  if constexpr (sizeof(T) == 2) {
+    V4L_HIP_CHECK(lds_limit<&bwd_conv_kernel<T, true>>(BwdConvLds<T>::bytes));
+    V4L_HIP_CHECK(lds_limit<&bwd_conv_kernel<T, false, true>>(BwdConvLds<T, true>::bytes));
+    V4L_HIP_CHECK(lds_limit<&bwd_conv_kernel<T, true, true>>(BwdConvLds<T, true>::bytes));
+  }
   // c1 / c2 in T: what the training encoder of THIS workspace's last forward wrote (the mark is the workspace's c1 address, so a
   // forward of the same net over another workspace in between — HipNet.value() at another batch size — does not change it)
   const bool a16 = sizeof(T) == 2 && N->acts16_c1 != nullptr && N->acts16_c1 == c1;
   int nblk = std::min(n, CONV_BWD_MAX_BLOCKS);
   if (const char* e = getenv("V4L_CONV_BWD_BLOCKS")) nblk = std::max(1, std::min(nblk, atoi(e)));
+  // 16-bit modes: the conv weight-grads' operands by transposed LDS reads (csrc/bwd.h, TR). V4L_WGRAD_TR: 0 the gathers, 1 (default)
+  // dW2 / dW1 and dW3, 2 dW2 / dW1 only, 3 dW3 only — the same bits whatever it says
+  const int tr_sw = sizeof(T) == 2 ? sw_int("V4L_WGRAD_TR", 1) : 0;
+  const bool tr = tr_sw == 1 || tr_sw == 2, tr3 = tr_sw == 1 || tr_sw == 3;
   // dW3's launch runs beside the dense weight-grads on the other stream: fewer, fatter blocks cut its partial slabs (147 KB
   // per block, written here and read again by wgrad_reduce) until the launch itself becomes the longer branch. The balance
   // moved with the other branch: when the dense weight-grads took ~54 us, 64 blocks (53 us) won (357.8 / 364.2 / 367.6 K
@@ -691,37 +715,24 @@ static int conv_stack_bwd_fused(Ctx& c, const T* image, const int* rowidx, int n
   g_op = "conv.bwd";
   const double fl = 2.0 * n * (16.0 * 64 * 576 + 2.0 * 36 * 64 * 512 + 225.0 * 32 * 256);
   if constexpr (sizeof(T) == 2) {
-    if (a16) V4L_KLAUNCH("fused_conv_bwd", fl, c.s, (bwd_conv_kernel<T, true>), dim3(nblk), dim3(512), BwdConvLds<T>::bytes, c.s, a);
+    if (a16 && tr) V4L_KLAUNCH("fused_conv_bwd", fl, c.s, (bwd_conv_kernel<T, true, true>), dim3(nblk), dim3(512), (BwdConvLds<T, true>::bytes), c.s, a);
+    else if (a16) V4L_KLAUNCH("fused_conv_bwd", fl, c.s, (bwd_conv_kernel<T, true>), dim3(nblk), dim3(512), BwdConvLds<T>::bytes, c.s, a);
+    else if (tr) V4L_KLAUNCH("fused_conv_bwd", fl, c.s, (bwd_conv_kernel<T, false, true>), dim3(nblk), dim3(512), (BwdConvLds<T, true>::bytes), c.s, a);
   }
-  if (!a16) V4L_KLAUNCH("fused_conv_bwd", fl, c.s, bwd_conv_kernel<T>, dim3(nblk), dim3(512), BwdConvLds<T>::bytes, c.s, a);
+  if (!a16 && !tr) V4L_KLAUNCH("fused_conv_bwd", fl, c.s, bwd_conv_kernel<T>, dim3(nblk), dim3(512), BwdConvLds<T>::bytes, c.s, a);
   V4L_LAUNCH_CHECK();
+  c.conv3_args = a; c.conv3_blocks = nblk3; c.conv3_n = n; c.conv3_a16 = a16; c.conv3_tr = tr3;
   if (c.defer_conv3) {
-    c.conv3_args = a; c.conv3_blocks = nblk3; c.conv3_n = n; c.conv3_pending = true; c.conv3_a16 = a16;
+    c.conv3_pending = true;
     return 0;
   }
-  g_op = "conv3.wgrad";
-  if constexpr (sizeof(T) == 2) {
-    if (a16) V4L_KLAUNCH("fused_conv3_wgrad", 2.0 * n * 16 * 64 * 576, c.tn, (bwd_conv3_wgrad_kernel<T, true>), dim3(nblk3), dim3(256), 0, c.tn, a);
-  }
-  if (!a16) V4L_KLAUNCH("fused_conv3_wgrad", 2.0 * n * 16 * 64 * 576, c.tn, bwd_conv3_wgrad_kernel<T>, dim3(nblk3), dim3(256), 0, c.tn, a);
-  V4L_LAUNCH_CHECK();
-  return 0;
+  return conv3_wgrad_launch<T>(c, c.tn);
 }
 template <typename T>
 static int conv3_wgrad_deferred(Ctx& c, hipStream_t s) {
   if (!c.conv3_pending) return 0;
   c.conv3_pending = false;
-  g_op = "conv3.wgrad";
-  if constexpr (sizeof(T) == 2) {
-    if (c.conv3_a16)
-      V4L_KLAUNCH("fused_conv3_wgrad", 2.0 * c.conv3_n * 16 * 64 * 576, s, (bwd_conv3_wgrad_kernel<T, true>), dim3(c.conv3_blocks),
-                  dim3(256), 0, s, c.conv3_args);
-  }
-  if (!c.conv3_a16)
-    V4L_KLAUNCH("fused_conv3_wgrad", 2.0 * c.conv3_n * 16 * 64 * 576, s, bwd_conv3_wgrad_kernel<T>, dim3(c.conv3_blocks), dim3(256), 0, s,
-                c.conv3_args);
-  V4L_LAUNCH_CHECK();
-  return 0;
+  return conv3_wgrad_launch<T>(c, s);
 }
 
 // dc3: grad w.r.t. conv3's pre-activation [n*16][64]. Scratch dc2 [n*36][64], dc1 [n*225][32].
