@@ -249,7 +249,8 @@ int v4l_gauss_head_sd(const float* out_dev, const float* acts_dev, const float* 
 int v4l_cat_head(const float* logits_dev, const float* acts_dev, int n, int K, float* probs_dev, float* ent_dev, float* logp_dev,
                  void* stream);
 /* Categorical(probs).sample() (discrete_policies.py:143-144) by inverse CDF: idx_dev[i] = the first k whose running sum
- * probs[i][0] + .. + probs[i][k] (fp32, in that order) exceeds u_dev[i], K - 1 if rounding leaves none; u_dev: [n] uniforms in
+ * probs[i][0] + .. + probs[i][k] (fp32, in that order) exceeds u_dev[i]; if rounding leaves none (a row summing to <= 1 - 2^-24
+ * at u = 1 - 2^-24), the last k with probs[i][k] > 0, and K - 1 only for a row without one; u_dev: [n] uniforms in
  * [0, 1) from the caller's generator (torch.rand: not torch.multinomial's stream). deterministic != 0: the first argmax of the
  * row (eval_act), u_dev may be NULL. */
 int v4l_cat_sample(const float* probs_dev, const float* u_dev, int n, int K, int deterministic, int64_t* idx_dev, void* stream);

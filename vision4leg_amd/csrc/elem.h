@@ -424,8 +424,10 @@ __device__ __forceinline__ float cat_logp(const CatDist& d, int K, float a) {
     if (j < K && a == (float)j) lp = d.lg[j];
   return lp;
 }
-// Categorical.sample() by inverse CDF from one uniform u in [0, 1): the first k whose running sum p_0 + .. + p_k exceeds u,
-// K - 1 if rounding leaves none. u < 0: no draw, the first argmax (eval_act, discrete_policies.py:156-158).
+// Categorical.sample() by inverse CDF from one uniform u in [0, 1): the first k whose running sum p_0 + .. + p_k exceeds u.
+// The fp32 sum of a row can end at or below the largest uniform, 1 - 2^-24 (torch.rand draws multiples of 2^-24), and then no k
+// does: the pick is the last k with p_k > 0 — never a class of probability zero, which torch.multinomial cannot return either —
+// and K - 1 only for a row without one. u < 0: no draw, the first argmax (eval_act, discrete_policies.py:156-158).
 __device__ __forceinline__ int cat_pick(const CatDist& d, int K, float u) {
   int idx = K - 1;
   if (u < 0.f) {
@@ -437,13 +439,15 @@ __device__ __forceinline__ int cat_pick(const CatDist& d, int K, float u) {
     return idx;
   }
   float c = 0.f;
+  int last = K - 1;  // the last k with p_k > 0 (register select: no indexing)
   bool found = false;
 #pragma unroll
   for (int j = 0; j < CAT_CAP; ++j) {
     c += d.p[j];
+    if (j < K && d.p[j] > 0.f) last = j;
     if (!found && j < K && c > u) { idx = j; found = true; }
   }
-  return idx;
+  return found ? idx : last;
 }
 // the same pick from a row of probabilities [K] (v4l_cat_sample: what explore() draws from)
 __global__ __launch_bounds__(256) void cat_sample_kernel(const float* __restrict__ probs, const float* __restrict__ u, int n, int K,
