@@ -438,6 +438,34 @@ int v4l_trainer_kl_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, co
 int v4l_trainer_kl_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, int count, int use_graph,
                               void* stream);
 int v4l_trainer_kl_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays);
+/* (version 117) The opt-in KL-adaptive learning rates of a run of PPO updates (PPO(desired_kl=...)): the schedule = "adaptive" of
+ * legged_gym / rsl_rl, decided on the device. v4l_trainer_kl_adapt arms the trainer — call it after v4l_trainer_begin /
+ * _begin_guarded — or, with rec_all_dev = NULL, disarms it. rec_all_dev: float [U][4]. It refuses non-positive or non-finite
+ * numbers, factor <= 1, lr_min > lr_max, a communicator, a categorical policy and a trainer armed with v4l_trainer_kl_stop (which
+ * in turn refuses a trainer armed here). The updates of an armed run go through v4l_trainer_kl_adapt_update_next / _update_run, which
+ * follow v4l_trainer_update_next / _update_run's rules with a graph key (PPO's fields + the array) and handles of their own; a
+ * change of any of the four numbers drops their graphs. An armed update is PPO's update plus one single-block launch
+ * (kl_adapt_kernel) behind the policy's backward, in front of its clip + Adam launch, which is the plain one: this option never
+ * skips a step.
+ *   approx_kl[u] = mean_i(log pi_old(a_i|s_i)) - mean_i(log pi_theta(a_i|s_i))     as v4l_trainer_kl_stop forms it, in double
+ *   d[u] = -1 if approx_kl[u] > 2 * desired_kl,  +1 if approx_kl[u] < 0.5 * desired_kl,  0 otherwise (a NaN: 0)
+ *   d = -1: lr = fmax(lr / factor, lr_min)       d = +1: lr = fmin(lr * factor, lr_max)       for lr_pf and lr_vf, each in double
+ * There is no "approx_kl > 0" clause (rsl_rl's KL is analytic and cannot be negative; this one is an estimate that can be): a
+ * negative estimate raises the rates. The new rates go into the control block and hold FROM UPDATE u + 1 ON: update u's critic
+ * step is already taken (the critic goes first) and its policy step uses the step size formed when the update opened — rsl_rl
+ * applies the new rate to the same minibatch's step. It writes
+ *   rec_all_dev[u] = {approx_kl[u], d[u], (float)lr_pf, (float)lr_vf}     (the rates after the decision)
+ * v4l_trainer_lrs copies the control block's two rates out as doubles ({lr_pf, lr_vf}; it synchronises the stream): after a run,
+ * the rates its next update would have used, which the caller hands to the next v4l_trainer_begin. Single process only; the
+ * V-MPO, A2C and REINFORCE entry points refuse an armed trainer. */
+int v4l_trainer_kl_adapt(v4l_trainer* tr, double desired_kl, double factor, double lr_min, double lr_max, float* rec_all_dev,
+                         void* stream);
+int v4l_trainer_kl_adapt_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, int use_graph,
+                                     void* stream);
+int v4l_trainer_kl_adapt_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, int count, int use_graph,
+                                    void* stream);
+int v4l_trainer_kl_adapt_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays);
+int v4l_trainer_lrs(v4l_trainer* tr, double* out, void* stream);
 /* The next minibatch update, == PPO.update (ppo.py:125-153). use_graph=1: the launch sequence (~20 kernels) is
  * captured once per (rollout pointers, n, hyper-parameters) as a hipGraph and replayed; needs a non-default stream.
  * The first update of a configuration always runs eagerly. */

@@ -168,6 +168,11 @@ _SIGS = {
   "v4l_trainer_kl_update_next": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), C.c_int, _P]),
   "v4l_trainer_kl_update_run": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), C.c_int, C.c_int, _P]),
   "v4l_trainer_kl_graph_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+  "v4l_trainer_kl_adapt": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P]),
+  "v4l_trainer_kl_adapt_update_next": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), C.c_int, _P]),
+  "v4l_trainer_kl_adapt_update_run": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), C.c_int, C.c_int, _P]),
+  "v4l_trainer_kl_adapt_graph_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+  "v4l_trainer_lrs": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
   "v4l_trainer_update_next": (C.c_int, [_P, C.POINTER(Rollout), C.c_int, C.POINTER(PPOHyper), C.c_int, _P]),
   "v4l_host_cast_rows": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, _P, C.c_int, C.c_int]),
   "v4l_host_cast_simd": (C.c_int, []),

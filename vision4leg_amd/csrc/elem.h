@@ -1046,6 +1046,73 @@ __global__ __launch_bounds__(1024) void kl_stop_kernel(KlArgs q) {
     q.kl_all[(int64_t)u * 2 + 1] = latch ? 1.f : 0.f;
   }
 }
+
+// The KL-adaptive learning rates of PPO(desired_kl=...) (v4l_trainer_kl_adapt): legged_gym / rsl_rl's
+// schedule = "adaptive", decided on the device. Runs where kl_stop_kernel runs in a run armed with the early stop: behind the policy's
+// backward (the record is complete), in front of the actor's clip_adam_kernel. Single block, row-strided.
+//   approx_kl = mean_i(log pi_old(a_i|s_i)) - mean_i(log pi_theta(a_i|s_i))      the number kl_stop_kernel forms
+// with the log pi_old expressions of actor_row / actor_loss_sd_body's lpo spelled out once more, on purpose (neither the loss kernels'
+// row code nor kl_stop_kernel's is shared: DESIGN.md 7). Sum and subtraction in double. The decision
+//   d = -1 if approx_kl > hi (= 2 * desired_kl),  +1 if approx_kl < lo (= 0.5 * desired_kl),  0 otherwise (a NaN compares false twice)
+// has no "approx_kl > 0" clause: the estimate can be negative, and a negative one raises the rates. Both rates take the decision,
+// each with one double operation and its clamp:
+//   d = -1: lr = fmax(lr / factor, lr_min)        d = +1: lr = fmin(lr * factor, lr_max)
+// and go back into UpdCtl::lr_pf / lr_vf, which upd_begin_step reads when the NEXT update opens: this update's critic step is
+// behind this launch and its policy step uses the step_size[0] / decay[0] formed when the update opened. No other launch of the
+// update reads or writes the two words. rec[u] = {approx_kl, d, (float)lr_pf, (float)lr_vf} (the rates after the decision),
+// u = UpdCtl::upd_index (the closing clip_adam_kernel advances it after this launch).
+struct KlAdaptArgs {
+  const float *tmean, *tlogstd, *logp_old, *acts;  // tmean / tlogstd unused with a stored logp_old; tlogstd unused with sd
+  const int* rowidx;
+  int n, A, sd;
+  const float* st;       // the record being filled (ST_LP_MEAN)
+  const int* upd_index;  // &UpdCtl::upd_index of the open run
+  double *lr_pf, *lr_vf; // &UpdCtl::lr_pf, &UpdCtl::lr_vf
+  float* rec;            // [U][4]
+  double lo, hi, factor, lr_min, lr_max;
+};
+template <bool TANH>
+__global__ __launch_bounds__(1024) void kl_adapt_kernel(KlAdaptArgs q) {
+  const int n = q.n, A = q.A;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int slot = q.rowidx ? q.rowidx[i] : i;
+    float lpo = 0.f;
+    if (q.logp_old != nullptr) {
+      lpo = q.logp_old[slot];
+    } else {
+      const float* __restrict__ trow = q.tmean + (int64_t)i * OUT_LD;
+      for (int a = 0; a < A; ++a) {
+        const float act = q.acts[(int64_t)slot * A + a];
+        const float x = TANH ? tanh_pre(act) : act;
+        const float corr = TANH ? tanh_corr(act) : 0.f;
+        const float tls = fminf(fmaxf(q.sd ? trow[A + a] : q.tlogstd[a], LOG_SIG_MIN), LOG_SIG_MAX);
+        const float tsg = expf(tls), tlsg = logf(tsg);
+        const float dt = x - trow[a];
+        lpo += -(dt * dt) / (2.f * tsg * tsg) - tlsg - HALF_LOG_2PI - corr;
+      }
+    }
+    s += (double)lpo;
+  }
+  const Red4 r = block_red4(s, 0.0, 0.f, 0.f);
+  if (threadIdx.x == 0) {
+    const double kl = r.s / (double)n - (double)q.st[ST_LP_MEAN];
+    const int u = *q.upd_index;
+    const int d = kl > q.hi ? -1 : kl < q.lo ? 1 : 0;
+    double lp = *q.lr_pf, lv = *q.lr_vf;
+    if (d < 0) {
+      lp = fmax(lp / q.factor, q.lr_min);
+      lv = fmax(lv / q.factor, q.lr_min);
+    } else if (d > 0) {
+      lp = fmin(lp * q.factor, q.lr_max);
+      lv = fmin(lv * q.factor, q.lr_max);
+    }
+    *q.lr_pf = lp;
+    *q.lr_vf = lv;
+    float* out = q.rec + (int64_t)u * 4;
+    out[0] = (float)kl; out[1] = (float)d; out[2] = (float)lp; out[3] = (float)lv;
+  }
+}
 #pragma clang fp contract(fast)
 
 // Gaussian head post-processing for the policy API (continuous_policy.py:85-146,486-492): from the padded

@@ -300,4 +300,15 @@ struct v4l_trainer {
   int kexec_run_count = 0;
   bool kwarm = false;
   int64_t kl_captures = 0, kl_replays = 0;
+  // the KL-adaptive learning rates (v4l_trainer_kl_adapt): [U][4] floats {approx_kl, decision, lr_pf, lr_vf} per update, null:
+  // disarmed; ad_num = {desired_kl, factor, lr_min, lr_max}, baked into the captured kl_adapt launches. Entry points
+  // (v4l_trainer_kl_adapt_update_next / _update_run), key (GraphKey + the array) and handles of their own, like the early stop's
+  float* ad_all = nullptr;
+  double ad_num[4] = {0.0, 0.0, 0.0, 0.0};
+  A2cGraphKey dkey = {};
+  hipGraphExec_t dexec = nullptr;
+  hipGraphExec_t dexec_run = nullptr;
+  int dexec_run_count = 0;
+  bool dwarm = false;
+  int64_t ad_captures = 0, ad_replays = 0;
 };

@@ -2728,7 +2728,9 @@ const char* v4l_last_error(void) { return v4l::last_error(); }
 // 115: v4l_net_set_categorical (CategoricalDisPolicy, policies/discrete_policies.py:127-172: K = out_dim logits, one action index) — v4l_cat_head,
 // v4l_cat_sample, a2c_cat_loss_kernel / reinforce_cat_loss_kernel behind the A2C and REINFORCE entry points, act_finish_cat_kernel on the GENERAL step
 // 116: the opt-in KL early stop inside a run of PPO updates: v4l_trainer_kl_stop, v4l_trainer_kl_update_next / _update_run / _graph_counts (kl_stop_kernel, clip_adam_kernel<WD, true>)
-int v4l_version(void) { return 116; }  // 112: A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
+// 117: the opt-in KL-adaptive learning rates of a run of PPO updates: v4l_trainer_kl_adapt, v4l_trainer_kl_adapt_update_next / _update_run / _graph_counts,
+// v4l_trainer_lrs (kl_adapt_kernel)
+int v4l_version(void) { return 117; }  // 112: A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
 int v4l_abi_sizeof(int which) {
   return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) :
          which == 4 ? (int)sizeof(v4l_vmpo_hyper) : -1;  // (3 stays unassigned)
@@ -3480,7 +3482,14 @@ static void drop_kl_graph(v4l_trainer* tr) {
   tr->kexec_run_count = 0;
   tr->kwarm = false;
 }
+static void drop_kl_adapt_graph(v4l_trainer* tr) {
+  if (tr->dexec) { (void)hipGraphExecDestroy(tr->dexec); tr->dexec = nullptr; }
+  if (tr->dexec_run) { (void)hipGraphExecDestroy(tr->dexec_run); tr->dexec_run = nullptr; }
+  tr->dexec_run_count = 0;
+  tr->dwarm = false;
+}
 static void drop_graph(v4l_trainer* tr) {
+  drop_kl_adapt_graph(tr);
   drop_kl_graph(tr);
   drop_ppo_graph(tr);
   drop_vmpo_graph(tr);
@@ -3899,6 +3908,7 @@ static int check_vmpo_args(const v4l_trainer* tr, const v4l_rollout* ro, int n, 
   V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_vmpo: a categorical policy (v4l_net_set_categorical) runs under the A2C and REINFORCE updates "
               "only: the V-MPO loss kernel and its KL are Gaussian");
   V4L_REQUIRE(tr->kl_all == nullptr, "v4l_trainer_vmpo: no KL early stop (v4l_trainer_kl_stop) in a V-MPO run");
+  V4L_REQUIRE(tr->ad_all == nullptr, "v4l_trainer_vmpo: no KL-adaptive learning rates (v4l_trainer_kl_adapt) in a V-MPO run");
   V4L_REQUIRE(tr->vmpo != nullptr, "v4l_trainer_vmpo_actor_grads: no V-MPO state (v4l_trainer_vmpo_init)");
   V4L_REQUIRE(n <= tr->vmpo_n_max, "v4l_trainer_vmpo_actor_grads: n = %d is over the V-MPO block's n_max = %d", n, tr->vmpo_n_max);
   V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_vmpo_actor_grads: V-MPO runs in a single process");
@@ -4288,6 +4298,7 @@ static int check_a2c_args(const v4l_trainer* tr, const v4l_rollout* ro, int n, c
   V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_a2c: A2C runs in a single process");
   V4L_REQUIRE(tr->skip_all == nullptr, "v4l_trainer_a2c: no skipping of non-finite steps (v4l_trainer_begin_guarded) in an A2C run");
   V4L_REQUIRE(tr->kl_all == nullptr, "v4l_trainer_a2c: no KL early stop (v4l_trainer_kl_stop) in an A2C run");
+  V4L_REQUIRE(tr->ad_all == nullptr, "v4l_trainer_a2c: no KL-adaptive learning rates (v4l_trainer_kl_adapt) in an A2C run");
   return 0;
 }
 // a2c.py:76-77, 84-85 (values = vf(obs), vf_loss, vf_loss.backward()): v4l_trainer_critic_grads' launches for a state-MLP net with
@@ -4473,6 +4484,8 @@ static int check_reinforce_args(const v4l_trainer* tr, const v4l_rollout* ro, in
   V4L_REQUIRE(tr->skip_all == nullptr,
               "v4l_trainer_reinforce: no skipping of non-finite steps (v4l_trainer_begin_guarded) in a REINFORCE run");
   V4L_REQUIRE(tr->kl_all == nullptr, "v4l_trainer_reinforce: no KL early stop (v4l_trainer_kl_stop) in a REINFORCE run");
+  V4L_REQUIRE(tr->ad_all == nullptr,
+              "v4l_trainer_reinforce: no KL-adaptive learning rates (v4l_trainer_kl_adapt) in a REINFORCE run");
   return 0;
 }
 // reinforce.py:52-63 (pf.update(obs, acts), policy_loss, policy_loss.backward())
@@ -4552,6 +4565,8 @@ int v4l_trainer_kl_stop(v4l_trainer* tr, double target_kl, float* kl_all_dev, vo
   V4L_REQUIRE(target_kl > 0.0 && target_kl <= 3.0e38, "v4l_trainer_kl_stop: target_kl must be a positive finite number (got %g)", target_kl);
   V4L_REQUIRE(tr->comm == nullptr, "v4l_trainer_kl_stop: the KL early stop runs in a single process (each rank would decide on its own shard)");
   V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_kl_stop: the KL early stop belongs to the PPO update, which takes Gaussian policies");
+  V4L_REQUIRE(tr->ad_all == nullptr, "v4l_trainer_kl_stop: the trainer is armed with the KL-adaptive learning rates (v4l_trainer_kl_adapt): "
+              "one run takes one of the two");
   if (tr->kl_thresh != 1.5 * target_kl) drop_kl_graph(tr);  // (baked into the captured kl_stop launches; the array is in the key)
   tr->kl_all = kl_all_dev;
   tr->kl_thresh = 1.5 * target_kl;  // the factor of Spinning Up and Stable-Baselines3
@@ -4660,6 +4675,119 @@ int v4l_trainer_kl_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_
   V4L_REQUIRE(tr && captures && replays, "v4l_trainer_kl_graph_counts: null argument");
   *captures = tr->kl_captures;
   *replays = tr->kl_replays;
+  return 0;
+}
+
+// ---- the opt-in KL-adaptive learning rates of a run of PPO updates (PPO(desired_kl=...)). An armed update is
+// PPO's update with one more launch (kl_adapt_kernel behind the policy's backward, where an early-stop run has kl_stop_kernel);
+// both clip + Adam launches are the plain ones (no step is ever skipped by this option). Entry points, graph key and graph
+// handles of its own on the record-array driver, like the early stop's: v4l_trainer_update_next / _update_run, the
+// v4l_trainer_kl_update_* calls, the stages they call and their graphs are not touched.
+int v4l_trainer_kl_adapt(v4l_trainer* tr, double desired_kl, double factor, double lr_min, double lr_max, float* rec_all_dev,
+                         void* stream) {
+  (void)stream;  // (nothing to clear on the device: the rates of the run are those v4l_trainer_begin wrote)
+  V4L_REQUIRE(tr && tr->bound, "v4l_trainer_kl_adapt: the trainer is not bound");
+  if (rec_all_dev == nullptr) {  // disarm
+    tr->ad_all = nullptr;
+    return 0;
+  }
+  const double big = 1.0e300;
+  V4L_REQUIRE(desired_kl > 0.0 && desired_kl <= big, "v4l_trainer_kl_adapt: desired_kl must be a positive finite number (got %g)", desired_kl);
+  V4L_REQUIRE(factor > 1.0 && factor <= big, "v4l_trainer_kl_adapt: factor must be a finite number > 1 (got %g)", factor);
+  V4L_REQUIRE(lr_min > 0.0 && lr_min <= big && lr_max > 0.0 && lr_max <= big && lr_min <= lr_max,
+              "v4l_trainer_kl_adapt: lr_min and lr_max must be positive finite numbers with lr_min <= lr_max (got %g, %g)", lr_min, lr_max);
+  V4L_REQUIRE(tr->comm == nullptr, "v4l_trainer_kl_adapt: the adaptive rates run in a single process (each rank would decide on its own shard)");
+  V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_kl_adapt: the adaptive rates belong to the PPO update, which takes Gaussian policies");
+  V4L_REQUIRE(tr->kl_all == nullptr, "v4l_trainer_kl_adapt: the trainer is armed with the KL early stop (v4l_trainer_kl_stop): one run "
+              "takes one of the two");
+  const double num[4] = {desired_kl, factor, lr_min, lr_max};
+  if (memcmp(num, tr->ad_num, sizeof(num)) != 0) drop_kl_adapt_graph(tr);  // (baked into the captured kl_adapt launches; the array is in the key)
+  memcpy(tr->ad_num, num, sizeof(num));
+  tr->ad_all = rec_all_dev;
+  return 0;
+}
+static int check_kl_adapt_args(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, const float* rec_all_dev) {
+  int rc = check_update_args(tr, ro, n, hp);
+  if (rc) return rc;
+  V4L_REQUIRE(rec_all_dev != nullptr && rec_all_dev == tr->ad_all, "v4l_trainer_kl_adapt_update: arm the run first (v4l_trainer_kl_adapt, after v4l_trainer_begin)");
+  V4L_REQUIRE(tr->kl_all == nullptr, "v4l_trainer_kl_adapt_update: the trainer is armed with the KL early stop as well (v4l_trainer_kl_stop)");
+  V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_kl_adapt_update: the PPO loss kernels are Gaussian");
+  V4L_REQUIRE(hp->world_size == 1 && tr->comm == nullptr, "v4l_trainer_kl_adapt_update: the adaptive rates run in a single process");
+  return 0;
+}
+// kl_adapt_kernel behind the policy's backward, on the trainer's stream (launch_kl_stop's place and operands: the record is
+// complete, the target's head rows and the stored actions are where the loss launch read them)
+static int launch_kl_adapt(v4l_trainer* tr, const v4l_rollout* ro, int n, hipStream_t s) {
+  v4l_net *pf = tr->pf, *tp = tr->tpf;
+  const bool stored = ro->logp_old_dev != nullptr, sd = pf->sd();
+  float* ws_t = tr->ws + std::max(pf->layout(n).total, tr->vf->layout(n).total);
+  KlAdaptArgs q;
+  memset(&q, 0, sizeof(q));
+  q.tmean = stored ? nullptr : ws_t + tp->layout(n).out;
+  q.tlogstd = stored || sd ? nullptr : tp->p[tp->logstd];
+  q.logp_old = ro->logp_old_dev; q.acts = ro->acts_dev; q.rowidx = tr->rowidx_cur;
+  q.n = n; q.A = pf->act_dim(); q.sd = sd ? 1 : 0;
+  q.st = tr->stats_cur; q.upd_index = &tr->ctl->upd_index; q.lr_pf = &tr->ctl->lr_pf; q.lr_vf = &tr->ctl->lr_vf;
+  q.rec = tr->ad_all;
+  q.lo = 0.5 * tr->ad_num[0]; q.hi = 2.0 * tr->ad_num[0];  // rsl_rl's thresholds (exact in double)
+  q.factor = tr->ad_num[1]; q.lr_min = tr->ad_num[2]; q.lr_max = tr->ad_num[3];
+  g_op = "kl_adapt";
+  if (pf->cfg.tanh_action) V4L_KLAUNCH("kl_adapt", 0, s, kl_adapt_kernel<true>, dim3(1), loss_block(n), 0, s, q);
+  else V4L_KLAUNCH("kl_adapt", 0, s, kl_adapt_kernel<false>, dim3(1), loss_block(n), 0, s, q);
+  V4L_LAUNCH_CHECK();
+  return 0;
+}
+static int run_kl_adapt_update(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, void* stream) {
+  int rc;
+  if ((rc = v4l_trainer_critic_grads(tr, ro, n, hp, stream))) return rc;
+  if ((rc = v4l_trainer_critic_step(tr, hp, stream))) return rc;
+  if ((rc = v4l_trainer_actor_grads(tr, ro, n, hp, stream))) return rc;
+  if ((rc = launch_kl_adapt(tr, ro, n, (hipStream_t)stream))) return rc;
+  return v4l_trainer_actor_step(tr, hp, stream);
+}
+struct KlAdaptLearner {
+  static constexpr const char* what = "kl-adapt update";
+  static constexpr const char* next_name = "v4l_trainer_kl_adapt_update_next";
+  static constexpr const char* run_name = "v4l_trainer_kl_adapt_update_run";
+  static int check(const v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, const float* rec) {
+    return check_kl_adapt_args(tr, ro, n, hp, rec);
+  }
+  static int run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, float*, void* stream) {
+    return run_kl_adapt_update(tr, ro, n, hp, stream);
+  }
+  static RecGraphState state(v4l_trainer* tr) {
+    return {&tr->dkey, &tr->dexec, &tr->dexec_run, &tr->dexec_run_count, &tr->dwarm, &tr->ad_captures, &tr->ad_replays};
+  }
+  static void drop(v4l_trainer* tr) { drop_kl_adapt_graph(tr); }
+  // (as KlLearner: PPO's graphs, and the early stop's, bake the same descriptor tables in and stay)
+  static void drop_others(v4l_trainer* tr) { drop_vmpo_graph(tr); drop_a2c_graph(tr); drop_reinforce_graph(tr); }
+};
+int v4l_trainer_kl_adapt_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, int use_graph,
+                                     void* stream) {
+  V4L_REQUIRE(tr != nullptr, "v4l_trainer_kl_adapt_update_next: null argument");
+  return rec_update_next<KlAdaptLearner>(tr, ro, n, hp, tr->ad_all, use_graph, stream);
+}
+int v4l_trainer_kl_adapt_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, int count, int use_graph,
+                                    void* stream) {
+  V4L_REQUIRE(tr != nullptr, "v4l_trainer_kl_adapt_update_run: null argument");
+  return rec_update_run<KlAdaptLearner>(tr, ro, n, hp, tr->ad_all, count, use_graph, stream);
+}
+int v4l_trainer_kl_adapt_graph_counts(const v4l_trainer* tr, int64_t* captures, int64_t* replays) {
+  V4L_REQUIRE(tr && captures && replays, "v4l_trainer_kl_adapt_graph_counts: null argument");
+  *captures = tr->ad_captures;
+  *replays = tr->ad_replays;
+  return 0;
+}
+// The two learning rates of the control block as doubles ({lr_pf, lr_vf}: what v4l_trainer_begin wrote, or what the last
+// kl_adapt launch left: the rates the next update of the run would use). Synchronises the stream.
+int v4l_trainer_lrs(v4l_trainer* tr, double* out, void* stream) {
+  V4L_REQUIRE(tr && tr->bound && tr->ctl && out, "v4l_trainer_lrs: the trainer is not bound");
+  hipStream_t s = (hipStream_t)stream;
+  double h[2] = {0.0, 0.0};
+  static_assert(offsetof(UpdCtl, lr_vf) == offsetof(UpdCtl, lr_pf) + sizeof(double), "lr_pf and lr_vf are read with one copy");
+  V4L_HIP_CHECK(hipMemcpyAsync(h, (const char*)tr->ctl + offsetof(UpdCtl, lr_pf), sizeof(h), hipMemcpyDeviceToHost, s));
+  V4L_HIP_CHECK(hipStreamSynchronize(s));
+  out[0] = h[0]; out[1] = h[1];
   return 0;
 }
 

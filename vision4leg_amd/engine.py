@@ -621,6 +621,37 @@ class HipTrainer:
     """-> (armed-update graphs instantiated, their replays launched) since this trainer was created."""
     return self._graph_counts("v4l_trainer_kl_graph_counts")
 
+  # ---- the opt-in KL-adaptive learning rates (PPO(desired_kl=...), DESIGN.md 2.4): begin(), kl_adapt_arm(), then
+  # kl_adapt_update_next / kl_adapt_update_run, then lrs() for the rates the next run opens with
+  def kl_adapt_arm(self, rec_all, desired_kl, factor=1.5, lr_min=1e-5, lr_max=1e-2):
+    """Arm the run begin() just opened (v4l_trainer_kl_adapt). rec_all: float32 [U][4] device tensor, update u writes (approx_kl,
+    decision -1 / 0 / 1, lr_pf, lr_vf after the decision) there; the new rates hold from update u + 1 on. None disarms. Keep it at
+    one address from run to run: the graph is keyed on it. No step is skipped by this option: the host's step counts stay right."""
+    self._run = self._run + (rec_all,)  # keep alive
+    check(self.L.v4l_trainer_kl_adapt(self.h, float(desired_kl), float(factor), float(lr_min), float(lr_max), _ptr(rec_all),
+                                      _stream()), "v4l_trainer_kl_adapt")
+
+  def kl_adapt_update_next(self, ro, n, graph=True):
+    """The next update of an armed run (v4l_trainer_kl_adapt_update_next): PPO's update plus the kl_adapt launch, on graphs of
+    its own."""
+    self._call_update("v4l_trainer_kl_adapt_update_next", ro, n, (int(graph),), 1)
+
+  def kl_adapt_update_run(self, ro, n, count, graph=True):
+    """The next `count` updates of an armed run: with graph=True ONE hipGraph replay for all of them
+    (v4l_trainer_kl_adapt_update_run)."""
+    self._call_update("v4l_trainer_kl_adapt_update_run", ro, n, (int(count), int(graph)), int(count))
+
+  def kl_adapt_graph_counts(self):
+    """-> (adaptive-rate update graphs instantiated, their replays launched) since this trainer was created."""
+    return self._graph_counts("v4l_trainer_kl_adapt_graph_counts")
+
+  def lrs(self):
+    """-> (lr_pf, lr_vf): the two learning rates of the device's control block as Python floats (doubles, bit for bit; one
+    synchronise): what begin() wrote, or what the last kl_adapt launch left — the rates the run's next update would use."""
+    out = (C.c_double * 2)()
+    check(self.L.v4l_trainer_lrs(self.h, out, _stream()), "v4l_trainer_lrs")
+    return float(out[0]), float(out[1])
+
   # phases, for the data-parallel schedule (all-reduce between grads and step); begin() first
   def stats_cur(self):
     if getattr(self, "_stats_cur", None) is None or self._stats_cur_ctl is not self.ctl:

@@ -196,7 +196,8 @@ class PPO:
                  opt_epochs=10, clipped_value_loss=False, shuffle=True, tau=None, gae=True, env=None,
                  replay_buffer=None, collector=None, logger=None, grad_clip=None, discount=0.99, num_epochs=3000,
                  batch_size=128, device="cpu", save_interval=100, eval_interval=1, save_dir=None, skip_nonfinite_steps=False,
-                 save_train_state=False, resume=None, optimizer_kwargs=None, target_kl=None, **kwargs):
+                 save_train_state=False, resume=None, optimizer_kwargs=None, target_kl=None, desired_kl=None, kl_lr_factor=1.5,
+                 kl_lr_min=1e-5, kl_lr_max=1e-2, **kwargs):
         # torch.optim.Adam / AdamW, a functools.partial of either, or "Adam" / "AdamW" + optimizer_kwargs (JSON configs): resolved
         # the way the reference would build it, `optimizer_class(params, lr=..., eps=1e-5)` (a2c.py:30-40); anything else raises
         opt = hip_optim.resolve(optimizer_class, optimizer_kwargs, lr=plr, eps=self._call_eps)
@@ -225,6 +226,33 @@ class PPO:
         self.target_kl = target_kl
         self.last_kl_stop = None  # (epoch, index of the update that set the latch) of the last stopped run, or None
         self.kl_stops = 0         # runs (epochs) stopped so far; neither is part of the train state
+        # opt-in (config "desired_kl", "kl_lr_factor", "kl_lr_min", "kl_lr_max"): legged_gym / rsl_rl's adaptive learning rate,
+        # decided on the device after every minibatch update. None: nothing of an update changes.
+        nums = {"kl_lr_factor": kl_lr_factor, "kl_lr_min": kl_lr_min, "kl_lr_max": kl_lr_max}  # before anything touches a device
+        if desired_kl is not None:
+            nums["desired_kl"] = desired_kl
+        for key, val in nums.items():
+            ok = isinstance(val, (int, float, np.integer, np.floating)) and not isinstance(val, bool)
+            if not ok or not (0.0 < float(val) < float("inf")):
+                raise ValueError("vision4leg_amd: %s must be a positive finite number%s (got %r)"
+                                 % (key, " or None" if key == "desired_kl" else "", val))
+        if not float(kl_lr_factor) > 1.0:
+            raise ValueError("vision4leg_amd: kl_lr_factor must be > 1 (got %r)" % (kl_lr_factor,))
+        if float(kl_lr_min) > float(kl_lr_max):
+            raise ValueError("vision4leg_amd: kl_lr_min = %r is above kl_lr_max = %r" % (kl_lr_min, kl_lr_max))
+        if desired_kl is not None:
+            if target_kl is not None:
+                raise ValueError("vision4leg_amd: desired_kl and target_kl are two answers to one estimate (adapt the rates / stop "
+                                 "the epoch's steps): a PPO takes one of them")
+            forced = (os.environ.get("V4L_FORCE_DP_PHASES", "0") != "0" and torch.distributed.is_available()
+                      and torch.distributed.is_initialized())
+            if _dist_world() > 1 or forced:
+                raise NotImplementedError("vision4leg_amd: desired_kl runs in a single process: data parallel (world_size > 1 / "
+                                          "V4L_FORCE_DP_PHASES) each rank would adapt the rates on its own shard")
+            desired_kl = float(desired_kl)
+        self.desired_kl = desired_kl
+        self.kl_lr_factor, self.kl_lr_min, self.kl_lr_max = float(kl_lr_factor), float(kl_lr_min), float(kl_lr_max)
+        self.lr_changes = {"down": 0, "up": 0}  # decisions -1 / +1 taken so far (not part of the train state)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("vision4leg_amd: PPO needs a GPU device (got %s); there is no CPU path" % self.device)
@@ -592,8 +620,10 @@ class PPO:
     def update_per_epoch(self):
         with torch.cuda.device(self.device):
             self.process_epoch_samples()
-            atu.update_linear_schedule(self.pf_optimizer, self.current_epoch, self.num_epochs, self.plr)
-            atu.update_linear_schedule(self.vf_optimizer, self.current_epoch, self.num_epochs, self.vlr)
+            if getattr(self, "desired_kl", None) is None:
+                atu.update_linear_schedule(self.pf_optimizer, self.current_epoch, self.num_epochs, self.plr)
+                atu.update_linear_schedule(self.vf_optimizer, self.current_epoch, self.num_epochs, self.vlr)
+            # (desired_kl: the optimisers' rates are the ones the device left after the last run — rsl_rl's schedule = "adaptive")
             self.trainer.sync_target()  # copy_model_params_from_to(pf, target_pf), ppo.py:34
             if isinstance(self.replay_buffer, rb.DeviceOnPolicyReplayBuffer):
                 self._update_epoch_resident()
@@ -621,8 +651,14 @@ class PPO:
         U = len(rowidx)
         stats = torch.zeros(U, _lib.V4L_STATS, dtype=torch.float32, device=self.device)
         self.run_updates(ro, rowidx, stats)
-        flags = kl = None
-        if self.target_kl is not None:  # records, flags and KL columns share one allocation: still one device->host copy
+        flags = kl = ad = None
+        if self.desired_kl is not None:  # records, flags and the [U][4] columns share one allocation: still one device->host copy
+            rec = self._rec_buf.cpu()
+            host = rec[:U * _lib.V4L_STATS].view(U, _lib.V4L_STATS).numpy()
+            if self.skip_nonfinite_steps:
+                flags = rec[U * _lib.V4L_STATS:U * (_lib.V4L_STATS + 2)].view(torch.int32).view(U, 2).numpy()
+            ad = rec[U * (_lib.V4L_STATS + 2):].view(U, 4).numpy()
+        elif self.target_kl is not None:  # records, flags and KL columns share one allocation: still one device->host copy
             rec = self._rec_buf.cpu()
             host = rec[:U * _lib.V4L_STATS].view(U, _lib.V4L_STATS).numpy()
             if self.skip_nonfinite_steps:
@@ -639,20 +675,40 @@ class PPO:
         self._note_skipped(spf, svf)
         self._note_f16_saturation(float(host[:, _lib.ST_F16_SAT].sum()))
         for u, row in enumerate(host):
-            self.logger.add_update_info(self._info(row, None if flags is None else flags[u], None if kl is None else kl[u]))
+            self.logger.add_update_info(self._info(row, None if flags is None else flags[u], None if kl is None else kl[u],
+                                                   None if ad is None else ad[u]))
+            if ad is not None:
+                self._note_lr_decision(ad[u][1])
             if kl is not None and kl[u][1] != 0:  # the updates after the stop changed nothing: the logger gets none of them
                 self._note_kl_stop(u)
                 break
 
-    def _info(self, row, flags, kl=None):
-        """The logger's info dict of one update: the 18 reference keys, with the guard on skipped/pf and skipped/vf (0 / 1), and
-        with target_kl approx_kl and kl_stop (0 / 1)."""
+    def _info(self, row, flags, kl=None, adapt=None):
+        """The logger's info dict of one update: the 18 reference keys, with the guard on skipped/pf and skipped/vf (0 / 1), with
+        target_kl approx_kl and kl_stop (0 / 1), and with desired_kl approx_kl, lr_decision (-1 / 0 / 1), lr/pf and lr/vf (the
+        rates in force after the update, as the device's record holds them: floats)."""
         info = {k: float(row[j]) for j, k in enumerate(_lib.STAT_KEYS)}
         if flags is not None:
             info["skipped/pf"], info["skipped/vf"] = int(flags[0] != 0), int(flags[1] != 0)
         if kl is not None:
             info["approx_kl"], info["kl_stop"] = float(kl[0]), int(kl[1] != 0)
+        if adapt is not None:
+            info["approx_kl"], info["lr_decision"] = float(adapt[0]), int(adapt[1])
+            info["lr/pf"], info["lr/vf"] = float(adapt[2]), float(adapt[3])
         return info
+
+    def _note_lr_decision(self, d):
+        if d < 0:
+            self.lr_changes["down"] += 1
+        elif d > 0:
+            self.lr_changes["up"] += 1
+
+    def _take_device_lrs(self):
+        """desired_kl: after a run the optimisers carry the rates the device left, as doubles (HipTrainer.lrs()): the next run's
+        begin() is handed those, and state_dict() saves them."""
+        lr_pf, lr_vf = self.trainer.lrs()
+        self.pf_optimizer.param_groups[0]["lr"] = lr_pf
+        self.vf_optimizer.param_groups[0]["lr"] = lr_vf
 
     def _note_kl_stop(self, u):
         self.last_kl_stop = (self.current_epoch, int(u))
@@ -712,6 +768,40 @@ class PPO:
                 kl.copy_(self._kl_buf)
         cur.wait_stream(tr.stream)
 
+    def _run_updates_kl_adapt(self, ro, rowidx, stats, skip, kl):
+        """run_updates with desired_kl: the armed run (HipTrainer.kl_adapt_arm / kl_adapt_update_run, graphs of their own), by
+        run_updates' switches. Records, guard flags and the columns [U][4] (approx_kl, decision, lr_pf, lr_vf) share one
+        allocation. Afterwards the optimisers carry the rates the device left (read back as doubles)."""
+        tr = self.trainer
+        U, n = rowidx.shape
+        if getattr(self, "_rowidx_buf", None) is None or self._rowidx_buf.shape != rowidx.shape:
+            self._rowidx_buf = torch.empty_like(rowidx)
+            self._rec_buf = torch.zeros(U * (_lib.V4L_STATS + 6), dtype=torch.float32, device=self.device)
+            self._stats_buf = self._rec_buf[:U * _lib.V4L_STATS].view(U, _lib.V4L_STATS)
+            self._skip_buf = self._rec_buf[U * _lib.V4L_STATS:U * (_lib.V4L_STATS + 2)].view(torch.int32).view(U, 2)
+            self._kl_buf = self._rec_buf[U * (_lib.V4L_STATS + 2):].view(U, 4)
+        self._rowidx_buf.copy_(rowidx)
+        cur = torch.cuda.current_stream(self.device)
+        tr.stream.wait_stream(cur)
+        with torch.cuda.stream(tr.stream):
+            tr._pre(n)
+            tr.begin(self._rowidx_buf, self._stats_buf, self.pf_optimizer.lr, self.vf_optimizer.lr,
+                     self._skip_buf if self.skip_nonfinite_steps else None)
+            tr.kl_adapt_arm(self._kl_buf, self.desired_kl, self.kl_lr_factor, self.kl_lr_min, self.kl_lr_max)
+            self.training_update_num += U
+            if self.use_graph and os.environ.get("V4L_EPOCH_GRAPH", "1") != "0":
+                tr.kl_adapt_update_run(ro, n, U, graph=True)
+            else:
+                for _ in range(U):
+                    tr.kl_adapt_update_next(ro, n, graph=self.use_graph)
+            stats.copy_(self._stats_buf)
+            if skip is not None:
+                skip.copy_(self._skip_buf)
+            if kl is not None:
+                kl.copy_(self._kl_buf)
+            self._take_device_lrs()
+        cur.wait_stream(tr.stream)
+
     def run_updates(self, ro, rowidx, stats, skip=None, kl=None):
         """All minibatch updates of an epoch: rowidx [U][n] int32 (device), stats [U][V4L_STATS] (device); skip: None or an
         int32 [U][2] device tensor that receives the guard's skipped-step flags (skip_nonfinite_steps); kl (target_kl only): None
@@ -719,7 +809,11 @@ class PPO:
         set the latch is skipped on the device; the launches still run (a stop saves no GPU time here).
         The whole run is ONE hipGraph replay on the trainer's stream (round 6; one replay per update with V4L_EPOCH_GRAPH=0) — on one
         GPU, and data-parallel with the library's own communicator (V4L_DP_COMM=rccl: both all-reduces are nodes of that graph). With torch.distributed doing the exchange
-        (the data-parallel default) an update is four eager phases with one all-reduce per optimiser step between them."""
+        (the data-parallel default) an update is four eager phases with one all-reduce per optimiser step between them.
+        With desired_kl, kl is None or a float32 [U][4] device tensor that receives (approx_kl, decision, lr_pf, lr_vf) per update,
+        and the optimisers' rates are afterwards those the device left."""
+        if self.desired_kl is not None:
+            return self._run_updates_kl_adapt(ro, rowidx, stats, skip, kl)
         if self.target_kl is not None:
             return self._run_updates_kl(ro, rowidx, stats, skip, kl)
         tr = self.trainer
@@ -800,9 +894,16 @@ class PPO:
             ro = HipTrainer.rollout(self._stage[0], self._stage[1], *arrays)
             stats = torch.zeros(1, _lib.V4L_STATS, dtype=torch.float32, device=dev)
             skip = torch.zeros(1, 2, dtype=torch.int32, device=dev) if self.skip_nonfinite_steps else None
-            kl = None
+            kl = ad = None
             tr = self.trainer
-            if self.target_kl is not None:  # a run of one armed update, eager like the one below
+            if self.desired_kl is not None:  # a run of one update armed with the adaptive rates, eager like the ones below
+                ad = torch.zeros(1, 4, dtype=torch.float32, device=dev)
+                tr._pre(n)
+                tr.begin(None, stats, self.pf_optimizer.lr, self.vf_optimizer.lr, skip)
+                tr.kl_adapt_arm(ad, self.desired_kl, self.kl_lr_factor, self.kl_lr_min, self.kl_lr_max)
+                tr.kl_adapt_update_next(ro, n, graph=False)
+                self._take_device_lrs()  # the next update(batch) opens with them
+            elif self.target_kl is not None:  # a run of one armed update, eager like the one below
                 kl = torch.zeros(1, 2, dtype=torch.float32, device=dev)
                 tr._pre(n)
                 tr.begin(None, stats, self.pf_optimizer.lr, self.vf_optimizer.lr, skip)
@@ -817,12 +918,16 @@ class PPO:
             host = stats[0].cpu().numpy()
             flags = skip.cpu().numpy() if skip is not None else None
             klh = kl.cpu().numpy() if kl is not None else None
+            adh = ad.cpu().numpy() if ad is not None else None
+        if adh is not None:
+            self._note_lr_decision(adh[0][1])
         # the device-side tripwire, as in _update_epoch_resident
         spf, svf = _check_update_records(host[None], flags, self.skip_nonfinite_steps,
                                          lambda u: "minibatch update %d" % self.training_update_num)
         self._note_skipped(spf, svf)
         self._note_f16_saturation(float(host[_lib.ST_F16_SAT]))
-        return self._info(host, None if flags is None else flags[0], None if klh is None else klh[0])
+        return self._info(host, None if flags is None else flags[0], None if klh is None else klh[0],
+                          None if adh is None else adh[0])
 
     # ---- outer loop (rl_algo.py:97-168) ----------------------------------------------------------------
     def train(self):

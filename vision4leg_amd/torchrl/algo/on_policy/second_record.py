@@ -36,6 +36,9 @@ class _SecondRecordPPO(PPO):
         if kwargs.get("target_kl") is not None:
             raise NotImplementedError("vision4leg_amd: %s does not take target_kl (the KL early stop belongs to PPO's update: "
                                       "its passes over the same samples, its ratio's log pi_old)" % name)
+        if kwargs.get("desired_kl") is not None:
+            raise NotImplementedError("vision4leg_amd: %s does not take desired_kl (the KL-adaptive learning rates belong to PPO's "
+                                      "update: its passes over the same samples, its ratio's log pi_old)" % name)
         if kwargs.get("save_train_state") or kwargs.get("resume") is not None:
             raise NotImplementedError("vision4leg_amd: %s does not save or resume a train state (what its update adds is not part "
                                       "of it); snapshot() writes the reference's model files" % name)
