@@ -172,8 +172,12 @@ int v4l_net_create(const v4l_net_cfg* cfg, v4l_net** out);
  * parameter whose action is ONE index, stored as a float in [n][1] action rows: v4l_trainer_create (pf and target_pf both
  * flagged) and v4l_actor_create take it as pf. It runs under the A2C and REINFORCE updates (a2c.py:61-74 and reinforce.py:52-61
  * read log_prob and ent only; a2c.py:63-65,97-102 log std/* only `if 'std' in out`), with a2c_cat_loss_kernel /
- * reinforce_cat_loss_kernel in the Gaussian loss launches' place and the records' std/* slots left as cleared; the PPO and V-MPO
- * entry points refuse it. Its rollout step is always the GENERAL route (v4l_actor_route) with act_finish_cat_kernel as epilogue:
+ * reinforce_cat_loss_kernel in the Gaussian loss launches' place and the records' std/* slots left as cleared, and (version 118)
+ * under the PPO update — v4l_trainer_actor_grads, v4l_trainer_update_next, v4l_trainer_update_run — with actor_loss_cat_kernel in
+ * actor_loss_kernel's place, the record's four log_std slots left as cleared and log pi_old either stored (logp_old_dev, as
+ * act_finish_cat_kernel files it) or taken from the frozen target's logits rows; in a single process. The V-MPO entry points,
+ * v4l_trainer_kl_stop, v4l_trainer_kl_update_*, v4l_trainer_kl_adapt and v4l_trainer_kl_adapt_update_* refuse it: their log pi_old
+ * code is Gaussian. Its rollout step is always the GENERAL route (v4l_actor_route) with act_finish_cat_kernel as epilogue:
  * `eps_dev` of the step entry points then carries [E] uniforms in [0, 1), one per env — the action is the inverse-CDF index of
  * v4l_cat_sample — or negative numbers for the first argmax (eval_act, discrete_policies.py:156-158); action_dev is [E][1],
  * mean_dev / std_dev are not written. */

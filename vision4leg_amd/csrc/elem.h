@@ -993,6 +993,71 @@ __device__ __forceinline__ void actor_loss_sd_body(const ActorArgs& p) {
 template <bool TANH>
 __global__ __launch_bounds__(1024) void actor_loss_sd_kernel(ActorArgs p) { actor_loss_sd_body<TANH>(p); }
 
+// The sibling for CategoricalDisPolicy (policies/discrete_policies.py:160-172: log_prob and entropy of
+// Categorical(softmax(logits))) — PPODiscrete's loss launch, in actor_loss_kernel's position with its record. p.mean: the logits
+// rows [n][OUT_LD] (the frozen target's in p.tmean), p.A = K, p.acts: [slots][1] action indices as floats; p.logstd, p.tlogstd,
+// p.dlogstd and p.tanh_action are unused. log pi_old is the stored rollout value, or the target's log-softmax at the action.
+// Per row, with p = softmax(z), H its entropy and dlp the clipped surrogate's slope of actor_row:
+//   policy_loss = -mean_i(min(ratio_i an_i, clamp(ratio_i) an_i)) - ent_coef mean_i(H_i)
+//   d z_j = dlp ([j == a] - p_j) + (ent_coef / n) p_j (log p_j + H)            (dH / dz_j = -p_j (log p_j + H))
+// through grad_out, columns K .. 15 exactly zero. The four log_std/* slots stay as the caller cleared them. Single block.
+// The target's CatDist is reduced to its one log p before the live row's is built: a thread never holds both.
+__global__ __launch_bounds__(1024) void actor_loss_cat_kernel(ActorArgs p) {
+  const int n = p.n, K = p.A;
+  const bool stored = p.logp_old != nullptr;
+  const float amean = p.st[ST_ADV_MEAN], astd = p.st[ST_ADV_STD];
+  const float dent = p.ent_coef * p.inv_n;
+  double s_lp = 0.0, s_lp2 = 0.0, s_sur = 0.0, s_ent = 0.0;
+  int sat = 0;
+  float lp_mx = -INFINITY, lp_mn = INFINITY, r_mx = -INFINITY, r_mn = INFINITY;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int slot = p.rowidx ? p.rowidx[i] : i;
+    const float act = p.acts[slot];
+    float lpo;
+    if (stored) {
+      lpo = p.logp_old[slot];  // stored when the action was taken (== the target policy's)
+    } else {
+      const CatDist t = cat_dist(p.tmean + (int64_t)i * OUT_LD, K);
+      lpo = cat_logp(t, K, act);
+    }
+    const CatDist d = cat_dist(p.mean + (int64_t)i * OUT_LD, K);
+    const float lp = cat_logp(d, K, act);
+    const float ratio = expf(lp - lpo);
+    const float an = (p.adv[slot] - amean) / (astd + 1e-5f);
+    const float pre = ratio * an;
+    const float clp = fminf(fmaxf(ratio, 1.f - p.clip), 1.f + p.clip) * an;
+    const float dlp = !(pre > clp) ? -p.inv_n * an * ratio : 0.f;  // (see actor_row)
+    s_sur += fminf(pre, clp);
+    s_ent += d.ent;
+    s_lp += lp; s_lp2 += (double)lp * lp;
+    lp_mx = fmaxf(lp_mx, lp); lp_mn = fminf(lp_mn, lp);
+    r_mx = fmaxf(r_mx, ratio); r_mn = fminf(r_mn, ratio);
+    float dz[CAT_CAP];
+#pragma unroll
+    for (int j = 0; j < CAT_CAP; ++j) {
+      dz[j] = 0.f;
+      if (j < K) {
+        const float hit = act == (float)j ? 1.f : 0.f;
+        dz[j] = grad_out(dlp * (hit - d.p[j]) + dent * d.p[j] * (d.lg[j] + d.ent), p.gscale, sat);
+      }
+    }
+    actor_store_dmean(p.dmean + (int64_t)i * OUT_LD, dz, true);
+  }
+  const Red4 r1 = block_red4(s_lp, s_lp2, lp_mx, lp_mn);
+  const Red4 r2 = block_red4(s_sur, (double)sat, r_mx, r_mn);
+  const Red4 r3 = block_red4(s_ent, 0.0, 0.f, 0.f);
+  if (threadIdx.x == 0) {
+    float* st = p.st;
+    const double lpm = r1.s / n;
+    st[ST_PI_LOSS] = (float)(-(r2.s / n) - (double)p.ent_coef * (r3.s / n));  // ppo.py:69 with ent.mean()
+    st[ST_LP_MEAN] = (float)lpm;
+    st[ST_LP_STD] = (float)sqrt(fmax(0.0, (r1.s2 - n * lpm * lpm) / (double)(n - 1)));
+    st[ST_LP_MAX] = r1.mx; st[ST_LP_MIN] = r1.mn;
+    st[ST_RATIO_MAX] = r2.mx; st[ST_RATIO_MIN] = r2.mn;
+    if (p.gscale != 1.f) st[ST_F16_SAT] += (float)r2.s2;
+  }
+}
+
 // The KL early stop of PPO(target_kl=...) (v4l_trainer_kl_stop). Runs after the actor's loss launch has completed
 // the record (behind the policy's backward) and before the actor's clip_adam_kernel. Single block, row-strided.
 //   approx_kl = mean_i(log pi_old(a_i|s_i)) - mean_i(log pi_theta(a_i|s_i))      ((logp_old - logp).mean(), Spinning Up's PPO)

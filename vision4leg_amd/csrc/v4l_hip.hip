@@ -2662,6 +2662,12 @@ static int launch_actor_loss_sd(hipStream_t s, const ActorArgs& aa, dim3 blk) {
   return 0;
 }
 
+// the same for a categorical policy (v4l_net_set_categorical; actor_loss_cat_kernel: logits rows, one action index per row)
+static int launch_actor_loss_cat(hipStream_t s, const ActorArgs& aa, dim3 blk) {
+  V4L_KLAUNCH("actor_loss", 0, s, actor_loss_cat_kernel, dim3(1), blk, 0, s, aa);
+  return 0;
+}
+
 // V-MPO: the row selection and the single-block loss launch (csrc/elem.h)
 static int launch_vmpo_select(hipStream_t s, const float* adv, const int* rowidx, int n, int* sel) {
   g_op = "select";
@@ -2730,7 +2736,9 @@ const char* v4l_last_error(void) { return v4l::last_error(); }
 // 116: the opt-in KL early stop inside a run of PPO updates: v4l_trainer_kl_stop, v4l_trainer_kl_update_next / _update_run / _graph_counts (kl_stop_kernel, clip_adam_kernel<WD, true>)
 // 117: the opt-in KL-adaptive learning rates of a run of PPO updates: v4l_trainer_kl_adapt, v4l_trainer_kl_adapt_update_next / _update_run / _graph_counts,
 // v4l_trainer_lrs (kl_adapt_kernel)
-int v4l_version(void) { return 117; }  // 112: A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
+// 118: the PPO update takes a categorical policy (PPODiscrete): actor_loss_cat_kernel behind v4l_trainer_actor_grads / _update_next / _update_run, log pi_old
+// stored (act_finish_cat_kernel) or from the frozen target's logits rows; V-MPO, the KL early stop and the KL-adaptive rates keep refusing the flag
+int v4l_version(void) { return 118; }  // 112: A2C on state-MLP nets: v4l_trainer_a2c_critic_grads / _actor_grads / _update_next / _update_run / _graph_counts, V4L_A2C_STATS; V-MPO updates as hipGraph replays: v4l_trainer_vmpo_update_next / _update_run / _graph_counts; V-MPO: v4l_vmpo_hyper, v4l_trainer_vmpo_* / v4l_vmpo_select; v4l_ppo_hyper.weight_decay / decoupled_weight_decay (Adam's L2 and AdamW); v4l_net_cfg.activation (V4L_ACT_TANH on V4L_NET_MLP); per-optimiser Adam step counts; v4l_trainer_begin_guarded (opt-in skip of non-finite steps) / v4l_trainer_steps
 int v4l_abi_sizeof(int which) {
   return which == 0 ? (int)sizeof(v4l_net_cfg) : which == 1 ? (int)sizeof(v4l_ppo_hyper) : which == 2 ? (int)sizeof(v4l_rollout) :
          which == 4 ? (int)sizeof(v4l_vmpo_hyper) : -1;  // (3 stays unassigned)
@@ -3599,6 +3607,8 @@ static int check_update_args(const v4l_trainer* tr, const v4l_rollout* ro, int n
   V4L_REQUIRE(hp->world_size >= 1, "v4l_trainer: world_size must be >= 1");
   V4L_REQUIRE(!tr->pf->sd() || (hp->world_size == 1 && tr->comm == nullptr),
               "v4l_trainer: a V4L_LOGSTD_HEAD policy (GaussianContPolicy) runs in a single process");
+  V4L_REQUIRE(!tr->pf->cat() || (hp->world_size == 1 && tr->comm == nullptr),
+              "v4l_trainer: a categorical policy (v4l_net_set_categorical) runs in a single process");
   if (int rc = check_hyper(hp)) return rc;
   V4L_REQUIRE(tr->comm == nullptr || hp->world_size == tr->comm_world,
               "v4l_trainer: hyper.world_size (%d) differs from the communicator's (%d)", hp->world_size, tr->comm_world);
@@ -3756,8 +3766,6 @@ int v4l_trainer_critic_step(v4l_trainer* tr, const v4l_ppo_hyper* hp, void* stre
 int v4l_trainer_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const v4l_ppo_hyper* hp, void* stream) {
   int rc = check_update_args(tr, ro, n, hp);
   if (rc) return rc;
-  V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_actor_grads: a categorical policy (v4l_net_set_categorical) runs under the A2C and REINFORCE updates only: the PPO "
-              "loss kernels are Gaussian");
   hipStream_t s = (hipStream_t)stream;
   v4l_net *pf = tr->pf, *tp = tr->tpf;
   float* st = tr->stats_cur;
@@ -3799,6 +3807,16 @@ int v4l_trainer_actor_grads(v4l_trainer* tr, const v4l_rollout* ro, int n, const
   {
     ActorArgs aa;
     const bool sd = pf->sd();  // log sigma from the head row: no logstd parameter, its gradient leaves in the d(out) row
+    if (pf->cat()) {  // logits rows, A = K, one action index per row: actor_args' conventions plus the target's rows and the clip
+      aa = actor_args(tr, ro, n, rowidx);
+      aa.tmean = stored ? nullptr : ws_t + Lt.out;
+      aa.logp_old = ro->logp_old_dev; aa.inv_n = inv_n; aa.clip = hp->clip_para; aa.ent_coef = hp->entropy_coeff;
+      // (V4L_NET_MLP: neither the fused forward-loss-backward launch nor the heads' chain beside the statistics)
+      if ((rc = launch_actor_loss_cat(s, aa, loss_block(n)))) return rc;
+      V4L_LAUNCH_CHECK();
+      PhaseScope ps("pf.bwd");
+      return v4l_net_backward(pf, ro->state_dev, ro->image_dev, rowidx, n, tr->ws, tr->g_pf, stream);
+    }
     aa.mean = tr->ws + Lp.out; aa.logstd = sd ? nullptr : pf->p[pf->logstd];
     aa.tmean = stored ? nullptr : ws_t + Lt.out; aa.tlogstd = stored || sd ? nullptr : tp->p[tp->logstd];
     aa.logp_old = ro->logp_old_dev; aa.acts = ro->acts_dev; aa.adv = ro->advs_dev; aa.rowidx = rowidx;
@@ -4130,8 +4148,6 @@ int v4l_trainer_update_next(v4l_trainer* tr, const v4l_rollout* ro, int n, const
                             void* stream) {
   int rc = check_update_args(tr, ro, n, hp);
   if (rc) return rc;
-  V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_update_next: a categorical policy (v4l_net_set_categorical) runs under the A2C and REINFORCE updates only: the PPO "
-              "loss kernels are Gaussian");
   hipStream_t s = (hipStream_t)stream;
   drop_vmpo_graph(tr);  // (a PPO update on a V-MPO trainer runs the policy's pass over n rows: other descriptor tables)
   drop_a2c_graph(tr);
@@ -4159,8 +4175,6 @@ int v4l_trainer_update_run(v4l_trainer* tr, const v4l_rollout* ro, int n, const 
                            void* stream) {
   int rc = check_update_args(tr, ro, n, hp);
   if (rc) return rc;
-  V4L_REQUIRE(!tr->pf->cat(), "v4l_trainer_update_run: a categorical policy (v4l_net_set_categorical) runs under the A2C and REINFORCE updates only: the PPO "
-              "loss kernels are Gaussian");
   V4L_REQUIRE(count >= 1, "v4l_trainer_update_run: count must be >= 1");
   hipStream_t s = (hipStream_t)stream;
   GraphKey key;

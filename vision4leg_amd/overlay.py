@@ -12,7 +12,8 @@ stays the reference's, so `starter/ppo_*.py` runs unchanged:
     overlay.install(a2c=True)         # + `torchrl.algo.A2C` on the HIP engine, state-MLP nets only (opt-in, like vmpo)
     overlay.install(reinforce=True)   # + `torchrl.algo.Reinforce` on the HIP engine, `networks.ZeroNet` -> this package's (opt-in)
     overlay.install(state_std=True)   # + `torchrl.policies.GaussianContPolicy` (log-std from the head) on the HIP engine (opt-in)
-    overlay.install(discrete=True)    # + `torchrl.policies.CategoricalDisPolicy` (discrete actions, under A2C / Reinforce) (opt-in)
+    overlay.install(discrete=True)    # + `torchrl.policies.CategoricalDisPolicy` (discrete actions, under A2C / Reinforce) and
+                                      #   `torchrl.algo.PPODiscrete`, its PPO learner, a name the reference does not have (opt-in)
 
 Rebinding is by name on every already-imported `torchrl.<pkg>` module that defines the name (the package and the
 sub-module that holds the class: `from torchrl.algo import PPO`, `from torchrl.algo.on_policy.ppo import PPO` and
@@ -71,6 +72,11 @@ STATE_STD_NAMES = {
 DISCRETE_NAMES = {
     "policies": ["CategoricalDisPolicy"],
 }
+# ... and its PPO learner: a name the reference does not have, so nothing is rebound; attached to the package for
+# `from torchrl.algo import PPODiscrete` (silently: the report names what was replaced)
+DISCRETE_NEW = {
+    "algo": ["PPODiscrete"],
+}
 
 _installed = {}
 
@@ -96,7 +102,8 @@ def install(fast_path=False, reference_package="torchrl", vmpo=False, a2c=False,
     reinforce=True also rebinds `torchrl.algo.Reinforce` and `torchrl.networks.ZeroNet` (the report gains "algo.Reinforce" only);
     without it both stay the reference's.
     state_std=True also rebinds `torchrl.policies.GaussianContPolicy` (and nothing else); without it that class stays the reference's.
-    discrete=True also rebinds `torchrl.policies.CategoricalDisPolicy` (and nothing else); without it that class stays the reference's."""
+    discrete=True also rebinds `torchrl.policies.CategoricalDisPolicy` and puts `PPODiscrete` on `torchrl.algo` (a new name: nothing
+    is rebound, the report does not list it); without it that class stays the reference's and `torchrl.algo` has no such name."""
     ref = importlib.import_module(reference_package)
     if getattr(ref, "__v4l_shell__", False):
         raise RuntimeError("vision4leg_amd.overlay: `%s` resolves to the HIP shell itself; put the reference "
@@ -129,6 +136,13 @@ def install(fast_path=False, reference_package="torchrl", vmpo=False, a2c=False,
             for name in names:
                 if not _rebind(ref_name, name, getattr(shell, name)):
                     raise RuntimeError("vision4leg_amd.overlay: the reference has no %s.%s to replace" % (ref_name, name))
+    if discrete:
+        for pkg, names in DISCRETE_NEW.items():
+            ref_name = "%s.%s" % (reference_package, pkg)
+            importlib.import_module(ref_name)
+            shell = importlib.import_module("vision4leg_amd.torchrl." + pkg)
+            for name in names:
+                _rebind(ref_name, name, getattr(shell, name), True)
     for wanted, table in ((vmpo, VMPO_NAMES), (a2c, A2C_NAMES), (state_std, STATE_STD_NAMES), (reinforce, REINFORCE_NAMES),
                           (discrete, DISCRETE_NAMES)):
         if not wanted:
